@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- atom-steps/s of one SevenNet-0 energy+force evaluation on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one energy+forces evaluation of the hot path (edge embedding -> 5
@@ -16,11 +16,20 @@ region; the per-step inputs of an MD step -- the edge vectors r_j - r_i [E,3] fp
 turn into -- are copied host -> device INSIDE every timed step (SURVEY.md section 8d: "graph already built;
 H2D of positions/edges included"; `--no-h2d` times the resident-input step instead).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+driver's contract fields (metric, value = atom-steps/s, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step) and what the timed steps themselves give.
+`--dump-outputs DIR` also writes what the last timed step returned (energy, atomic_energy,
+dE_dr, forces, virial; rank 0's brick for N > 1, with the total energy) as DIR/<name>.npy,
+float32 / float64, at most 64 MB in all; inputs and weights are seeded, so two builds can be
+compared output for output.  `--full` adds what takes passes of its own:
   roofline     -- dominant kernel class, achieved vs gfx950 peak, from HIP events
                   recorded around every launch of that class inside the timed steps
+  telemetry    -- shader clock / power / temperature over a repeat of the K steps, and the
+                  per-kernel-class breakdown of an untimed pass (config.*)
+  brick_proxy  -- with --brick-proxy W (N=1 only)
   cpu_baseline -- the CPU oracle (reference-equivalent PyTorch path) timed on this
-                  box's host cores on a bounded sample (N=1 only)
+                  box's host cores on a bounded sample (N=1 only; --no-cpu-baseline skips it)
 """
 import argparse
 import json
@@ -65,8 +74,11 @@ DTYPE_LABEL = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=10)
-    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=10, help='timed steps')
+    ap.add_argument('--warmup', type=int, default=3, help='untimed steps before them')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='also measure the roofline, telemetry and per-kernel breakdown, the brick '
+                    'proxy (--brick-proxy) and the CPU baseline: passes of their own beside the timed steps')
     ap.add_argument('--reps', type=int, default=0, help='diamond cells per axis; default per model: sevennet_0 23 (97 336 atoms), '
                     'sevennet_l3i5 19 (54 872, BASELINE config 4), sevennet_mf_ompa 15 (27 000)')
     ap.add_argument('--model', default='sevennet_0', choices=['sevennet_0', 'sevennet_l3i5', 'sevennet_mf_ompa'])
@@ -98,13 +110,18 @@ def parse():
                          "hands over), 'edges' (the fp32 edge vectors [E,3], round-2 behaviour), 'none' (inputs resident)")
     ap.add_argument('--no-h2d', action='store_true', help="same as --h2d none")
     ap.add_argument('--brick-proxy', type=int, default=0, metavar='W',
-                    help='N = 1 only: after the timed region also time rank 0\'s brick of a W-way spatial decomposition of the same cell '
+                    help='--full, N = 1 only: after the timed region also time rank 0\'s brick of a W-way spatial decomposition of the same cell '
                          'on this GPU (ghost rows, interior / boundary split, a self-loop halo that packs, copies and accumulates the '
                          'same rows the RCCL exchange would, on the halo stream) and report it as `brick_proxy` beside the ideal N = 1 step / W')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-reps', type=int, default=11, help='CPU-baseline sample: cells per axis (11 -> the 10 648-atom cell of BASELINE '
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--cpu-reps', type=int, default=11, help='--full, CPU-baseline sample: cells per axis (11 -> the 10 648-atom cell of BASELINE '
                     'config 2, SURVEY.md 8(d), ~4 min; 6 -> only the 1728-atom cell that picks the thread count, ~1 min)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if a.brick_proxy and not a.full:
+        ap.error('--brick-proxy is measured by --full')
+    return a
 
 
 def model_config(name):
@@ -279,6 +296,27 @@ def cpu_baseline(cfg, sd, reps, small_reps=6):
                        f'{best} torch threads on {cpu_model_name()} ({phys} physical cores, {os.cpu_count()} logical CPUs); '
                        f'thread count chosen on the {len(pos_s)}-atom cell, atom-steps/s by thread count there: '
                        + ', '.join(f'{k}: {v[0]:.0f}' for k, v in runs.items()))
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # array data of --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: name -> float32 / float64 array as <directory>/<name>.npy, at most DUMP_LIMIT_BYTES in all.  An array that does
+    not fit (largest first) is cut to a sorted sample of its rows drawn with a fixed seed: the same rows for the same shape on every
+    run and every build."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(v.nbytes for v in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].nbytes):
+        if total <= DUMP_LIMIT_BYTES:
+            break
+        v = arrays[name]
+        keep = max(1, (DUMP_LIMIT_BYTES - (total - v.nbytes)) // (v.nbytes // len(v)))
+        arrays[name] = v[np.sort(np.random.default_rng(0).choice(len(v), size=keep, replace=False))]
+        total -= v.nbytes - arrays[name].nbytes
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(directory, name + '.npy'), v)
 
 
 class SelfLoopHalo:
@@ -562,21 +600,22 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    # Per-kernel HIP events cost time on this platform (a timestamp packet per record: the step with ~120 records
-    # ran 15 % slower than without).  So: (1) one untimed pass with every class bracketed picks the dominant class,
-    # (2) the TIMED steps bracket only that class (6 records per step) -- its average launch duration is measured
-    # live inside the timed region, as the contract asks --, (3) a last untimed pass gives the full breakdown.
-    eng.events, eng.event_filter = [], None
-    eng.compute(graph, halo=halo)
-    fence()
-    probe = {}
-    for name, t in eng.kernel_times_ms().items():
-        probe[name] = float(np.sum(t))
-    models0 = {}
-    for ls, L in zip(eng.spec.layers, eng.layers):
-        models0.update(kernel_model(ls, graph.n_local, graph.n_edges, getattr(L, 'mlp_tail', False), eng.spec.n_basis))
-    dominant0 = max((k for k in probe if k in models0), key=lambda k: probe[k])
-    eng.events, eng.event_filter = [], {dominant0}
+    if a.full:
+        # Per-kernel HIP events cost time on this platform (a timestamp packet per record: the step with ~120 records
+        # ran 15 % slower than without).  So: (1) one untimed pass with every class bracketed picks the dominant class,
+        # (2) the TIMED steps bracket only that class (6 records per step) -- its average launch duration is measured
+        # live inside the timed region, as the contract asks --, (3) a last untimed pass gives the full breakdown.
+        eng.events, eng.event_filter = [], None
+        eng.compute(graph, halo=halo)
+        fence()
+        probe = {}
+        for name, t in eng.kernel_times_ms().items():
+            probe[name] = float(np.sum(t))
+        models0 = {}
+        for ls, L in zip(eng.spec.layers, eng.layers):
+            models0.update(kernel_model(ls, graph.n_local, graph.n_edges, getattr(L, 'mlp_tail', False), eng.spec.n_basis))
+        dominant0 = max((k for k in probe if k in models0), key=lambda k: probe[k])
+        eng.events, eng.event_filter = [], {dominant0}
     # per-step durations for the MEDIAN ("median of >= 20 steps"): one HIP event between consecutive steps on the
     # compute stream (K + 1 records per K steps), read after the closing fence
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
@@ -588,17 +627,24 @@ def main():
     t_enq = time.perf_counter() - t0  # host time to enqueue K steps (kernels run asynchronously)
     fence()
     dt = time.perf_counter() - t0
-    # Shader clock / socket power / temperature this line was measured under (sevennet_amd/telemetry.py: librocm_smi64 on a side
-    # thread): the two dominant kernels run at the socket's power cap, so a 5 % swing between boxes is a clock swing unless shown
-    # otherwise.  Sampled over a REPEAT of the same K steps right behind the timed bracket, not inside it: the first version sampled
-    # inside and one step of twenty took 61 instead of 39.8 ms (the SMU query contends with command submission).
-    from sevennet_amd.telemetry import Sampler
-    with Sampler(dev_id) as tele:
-        t0t = time.perf_counter()
-        for i in range(a.steps):
-            step()
-        fence()
-        tele_ms = (time.perf_counter() - t0t) / a.steps * 1e3
+    e_total = out['energy'].clone()
+    if dist_mode:  # ranks hold partial energies of their bricks
+        dist.all_reduce(e_total)
+    if a.dump_outputs and rank == 0:   # copied off the device before anything else runs
+        outputs = {k: v.detach().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor)}
+        outputs['energy'] = e_total.cpu().numpy()
+    if a.full:
+        # Shader clock / socket power / temperature this line was measured under (sevennet_amd/telemetry.py: librocm_smi64 on a side
+        # thread): the two dominant kernels run at the socket's power cap, so a 5 % swing between boxes is a clock swing unless shown
+        # otherwise.  Sampled over a REPEAT of the same K steps right behind the timed bracket, not inside it: the first version sampled
+        # inside and one step of twenty took 61 instead of 39.8 ms (the SMU query contends with command submission).
+        from sevennet_amd.telemetry import Sampler
+        with Sampler(dev_id) as tele:
+            t0t = time.perf_counter()
+            for i in range(a.steps):
+                step()
+            fence()
+            tele_ms = (time.perf_counter() - t0t) / a.steps * 1e3
     per_step = torch.tensor([marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)], device=dev, dtype=torch.float64)
     if dist_mode:   # a step is over when the slowest rank is
         dist.all_reduce(per_step, op=dist.ReduceOp.MAX)
@@ -608,122 +654,120 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    timed_dom = eng.kernel_times_ms().get(dominant0, [])   # recorded by the Python host only
-    eng.events, eng.event_filter = [], None
-    for _ in range(min(a.steps, 3)):
-        eng.compute(graph, halo=halo)
-    fence()
-    n_break = min(a.steps, 3)
-    times = eng.kernel_times_ms()
-    eng.events = None
-
-    # ---- per-kernel-class time over the timed region -> dominant kernel + roofline
-    totals = {k: float(np.sum(v)) for k, v in times.items()}
-    counts = {k: len(v) for k, v in times.items()}
-    models = {}
-    for ls, L in zip(eng.spec.layers, eng.layers):
-        models.update(kernel_model(ls, graph.n_local, graph.n_edges, getattr(L, 'mlp_tail', False), eng.spec.n_basis))
-    # classes tagged '@side' ran on the second stream, overlapped with main-stream kernels: their event brackets
-    # are not exclusive time, so the dominant class is chosen among the main-stream ones
-    dominant = dominant0
-    # average launch duration of the dominant class: from the timed steps when the Python host sequenced them,
-    # from the breakdown pass when the native sequencer did (its launches are not bracketed)
-    avg_ms = float(np.mean(timed_dom)) if len(timed_dom) else totals[dominant] / counts[dominant]
-    km = models[dominant]
-    if km['bound'] == 'hbm':
-        ach = km['bytes'] / (avg_ms * 1e-3) / 1e9
-        roof = dict(bound='hbm', kernel=dominant, achieved=ach, peak=HBM_PEAK_GBS, unit='GB/s',
-                    frac=ach / HBM_PEAK_GBS, traffic=None, avg_ms=avg_ms,
-                    algorithmic_bytes_per_launch=km['bytes'],
-                    byte_model='SURVEY.md section 8(d): E (2*4*dx + 12 + 8 + 12) + N 4 dmid for a reverse launch, '
-                               'E (4 dx + 12 + 8) + N 4 dmid for a forward launch')
-        if 'bytes_incl_staging' in km:   # what the kernel really moves besides (Y, dY, h2, emb, g_emb): a second view
-            roof['frac_incl_staging'] = km['bytes_incl_staging'] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof['bytes_incl_staging_per_launch'] = km['bytes_incl_staging']
-        if 'flops' in km:  # fused kernels also carry the radial MLP's last layer on the matrix cores
-            n_prod = {4: 3, 3: 6, 2: 3, 1: 1}[a.terms]
-            roof['mfma'] = dict(algorithmic_flops_per_launch=km['flops'], bf16_products_per_flop=n_prod,
-                                achieved_tflops=km['flops'] * n_prod / (avg_ms * 1e-3) / 1e12, peak_tflops=MFMA_BF16_PEAK_TF,
-                                frac=km['flops'] * n_prod / (avg_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF)
-    else:
-        ach = km['flops'] / (avg_ms * 1e-3) / 1e12
-        roof = dict(bound='mfma', kernel=dominant, achieved=ach, peak=MFMA_F32_PEAK_TF, unit='TFLOP/s',
-                    frac=ach / MFMA_F32_PEAK_TF, traffic=None, avg_ms=avg_ms,
-                    algorithmic_flops_per_launch=km['flops'])
-    # HBM bytes per launch from the committed PMC passes of the same workload (profiles/README.md)
-    try:
-        import glob
-        pmc = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_hbm_traffic.json')))[-1]
-        with open(pmc) as f:
-            tr = json.load(f)
-        key = dominant.replace('conv_bwd_edge[', 'conv_bwd_edge_vec_').replace('conv_fwd_fused[', 'conv_fwdf_') \
-            .replace('conv_bwd_fused[', 'conv_bwdf_').replace('conv_fwd[', 'conv_fwd_') \
-            .replace('conv_bwd_node[', 'conv_bwd_node_').rstrip(']')
-        # a kernel class may be several kernels (one per x irrep block: <name>_k0, _k1, ...)
-        parts = [v for k, v in tr.items() if k == key or k.startswith(key + '_k') or k.startswith(key + '<')]
-        if world == 1 and a.reps == 23 and parts:
-            roof['traffic'] = sum(v['hbm_bytes_per_launch'] for v in parts)
-            roof['traffic_frac_of_peak'] = roof['traffic'] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof['traffic_source'] = os.path.basename(pmc) + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, gfx950-corrected)'
-            # the counters belong to the kernel SOURCE they were collected on: tools/collect_profiles.sh stamps the profile with
-            # the sha1 of every generated fused kernel; a kernel edited since then ships its figure marked stale, not silently
-            tag_ = dominant.split('[')[-1].rstrip(']')
-            now = fused_source_hashes().get(tag_)
-            then = (tr.get('__kernel_sources__') or {}).get(tag_)
-            roof['traffic_kernel_sha1'] = then
-            roof['traffic_stale'] = (then is None) or (now != then)
-            if roof['traffic_stale']:
-                roof['traffic_note'] = (f'PMC pass predates the current kernel source (profile: {then or "unstamped"}, tree: {now}); '
-                                        're-run tools/collect_profiles.sh')
-    except Exception:  # noqa: BLE001
-        pass
-    if any(k.endswith('@side') for k in totals):
-        roof['note'] = ("classes tagged '@side' (radial MLPs) run on a second HIP stream concurrently with the "
-                        "main-stream kernels: their event brackets overlap the others and are not exclusive time; "
-                        "avg_ms of the dominant kernel is measured with that concurrent work present")
     step_ms = dt / a.steps * 1e3
-    e_total = out['energy'].clone()
-    if dist_mode:  # ranks hold partial energies of their bricks
-        dist.all_reduce(e_total)
-    roof['kernel_ms_per_step'] = {k: round(v / n_break, 4) for k, v in sorted(totals.items(), key=lambda kv: -kv[1])}
-    roof['avg_ms_source'] = 'HIP events inside the timed steps' if len(timed_dom) else 'HIP events of an untimed pass of the same kernels (native host)'
-    # whole step: SURVEY.md 8(d)'s algorithmic BYTES against the HBM peak, and the arithmetic the engine actually SCHEDULES (pruned
-    # paths, sparse Clebsch-Gordan tensors, split-precision products counted once per matrix-core product issued) against the
-    # pipes it runs on.  SURVEY's dense-CG fp32 FLOP count is kept as information only: divided into a step that runs the dense
-    # contractions as low-precision splits on the 2.5-PF pipe and prunes unread paths it gave "fractions" above 1.
-    if a.model in STEP_WORK:
-        sb, sf = (v * n_atoms for v in STEP_WORK[a.model])
-        t = dt / a.steps * world   # GPU-seconds per step
-        sched = scheduled_work(eng, graph)
-        valu_peak = VALU_F32_PEAK_TF * 1e12
-        roof['step'] = dict(bytes=sb, frac_hbm=sb / t / (HBM_PEAK_GBS * 1e9), floor_ms_hbm=sb / (HBM_PEAK_GBS * 1e9) * 1e3,
-                            mfma_flops_issued=sched['mfma'], valu_flops=sched['valu'],
-                            frac_mfma_issued=sched['mfma'] * world / t / (MFMA_BF16_PEAK_TF * 1e12),
-                            frac_valu=sched['valu'] * world / t / valu_peak,
-                            valu_peak_tflops=VALU_F32_PEAK_TF, valu_measured_tflops_by_waves_per_simd=VALU_F32_MEASURED_TF,
-                            flops_survey_dense_fp32=sf,
-                            note='bytes: SURVEY.md 8(d) per atom-step (fwd + reverse, no cache credit, radial weights not '
-                                 'materialised) over 8 TB/s.  mfma_flops_issued: every 16x16x32 / 32x32x16 product the kernels issue '
-                                 '(in-kernel W2 products x3 for f16x3, node linears and hidden radial layers x6 for bf16x6) over the '
-                                 '2.5 PFLOP/s dense f16 / bf16 peak.  valu_flops: the sparse tensor-product arithmetic as generated '
-                                 '(forward: nnz(C) FMAs + pair products per channel; reverse: Clebsch-Gordan tensor contracted with the '
-                                 'harmonics per edge, two FMAs per nonzero (a, c) pair and three per x component per channel) over '
-                                 'the 157.3 TFLOP/s fp32 vector peak (SIMD-32: a wave64 instruction issues over 2 cycles); '
-                                 'valu_measured_tflops_by_waves_per_simd = what plain v_fma_f32 streams reach on this chip by occupancy '
-                                 '(one wave issues a vector instruction every ~7.5 cycles: tools/gpu/issue_probe, '
-                                 'profiles/r05_issue_rate_probe.txt).  flops_survey_dense_fp32 = SURVEY.md 8(d)\'s dense-CG count, for '
-                                 'reference only.')
+    if a.full:
+        timed_dom = eng.kernel_times_ms().get(dominant0, [])   # recorded by the Python host only
+        eng.events, eng.event_filter = [], None
+        for _ in range(min(a.steps, 3)):
+            eng.compute(graph, halo=halo)
+        fence()
+        n_break = min(a.steps, 3)
+        times = eng.kernel_times_ms()
+        eng.events = None
 
-    # ghost exchange of this rank per step: L-1 forward (width dx_t) + L-1 reverse exchanges + one force fold; bytes = rows
-    # sent + received; time = HIP-event brackets around the exchange calls (with the split exchange the brackets cover
-    # only the enqueue + the final wait, i.e. the part that is NOT hidden behind compute)
-    halo_ms, halo_n, halo_bytes = 0.0, 0, 0
-    if dist_mode:
-        halo_ms = sum(v for k, v in totals.items() if k.startswith('halo')) / n_break
-        rows = int(sum(len(s_) for s_ in bg.send_lists)) + int(graph.n_total - graph.n_local)
-        dims = [ls.si1.dim_out for ls in eng.spec.layers[1:]]
-        halo_n = 2 * len(dims) + 1
-        halo_bytes = rows * 4 * (2 * sum(dims) + 3)
+        # ---- per-kernel-class time over the timed region -> dominant kernel + roofline
+        totals = {k: float(np.sum(v)) for k, v in times.items()}
+        counts = {k: len(v) for k, v in times.items()}
+        models = {}
+        for ls, L in zip(eng.spec.layers, eng.layers):
+            models.update(kernel_model(ls, graph.n_local, graph.n_edges, getattr(L, 'mlp_tail', False), eng.spec.n_basis))
+        # classes tagged '@side' ran on the second stream, overlapped with main-stream kernels: their event brackets
+        # are not exclusive time, so the dominant class is chosen among the main-stream ones
+        dominant = dominant0
+        # average launch duration of the dominant class: from the timed steps when the Python host sequenced them,
+        # from the breakdown pass when the native sequencer did (its launches are not bracketed)
+        avg_ms = float(np.mean(timed_dom)) if len(timed_dom) else totals[dominant] / counts[dominant]
+        km = models[dominant]
+        if km['bound'] == 'hbm':
+            ach = km['bytes'] / (avg_ms * 1e-3) / 1e9
+            roof = dict(bound='hbm', kernel=dominant, achieved=ach, peak=HBM_PEAK_GBS, unit='GB/s',
+                        frac=ach / HBM_PEAK_GBS, traffic=None, avg_ms=avg_ms,
+                        algorithmic_bytes_per_launch=km['bytes'],
+                        byte_model='SURVEY.md section 8(d): E (2*4*dx + 12 + 8 + 12) + N 4 dmid for a reverse launch, '
+                                   'E (4 dx + 12 + 8) + N 4 dmid for a forward launch')
+            if 'bytes_incl_staging' in km:   # what the kernel really moves besides (Y, dY, h2, emb, g_emb): a second view
+                roof['frac_incl_staging'] = km['bytes_incl_staging'] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof['bytes_incl_staging_per_launch'] = km['bytes_incl_staging']
+            if 'flops' in km:  # fused kernels also carry the radial MLP's last layer on the matrix cores
+                n_prod = {4: 3, 3: 6, 2: 3, 1: 1}[a.terms]
+                roof['mfma'] = dict(algorithmic_flops_per_launch=km['flops'], bf16_products_per_flop=n_prod,
+                                    achieved_tflops=km['flops'] * n_prod / (avg_ms * 1e-3) / 1e12, peak_tflops=MFMA_BF16_PEAK_TF,
+                                    frac=km['flops'] * n_prod / (avg_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TF)
+        else:
+            ach = km['flops'] / (avg_ms * 1e-3) / 1e12
+            roof = dict(bound='mfma', kernel=dominant, achieved=ach, peak=MFMA_F32_PEAK_TF, unit='TFLOP/s',
+                        frac=ach / MFMA_F32_PEAK_TF, traffic=None, avg_ms=avg_ms,
+                        algorithmic_flops_per_launch=km['flops'])
+        # HBM bytes per launch from the committed PMC passes of the same workload (profiles/README.md)
+        try:
+            import glob
+            pmc = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_hbm_traffic.json')))[-1]
+            with open(pmc) as f:
+                tr = json.load(f)
+            key = dominant.replace('conv_bwd_edge[', 'conv_bwd_edge_vec_').replace('conv_fwd_fused[', 'conv_fwdf_') \
+                .replace('conv_bwd_fused[', 'conv_bwdf_').replace('conv_fwd[', 'conv_fwd_') \
+                .replace('conv_bwd_node[', 'conv_bwd_node_').rstrip(']')
+            # a kernel class may be several kernels (one per x irrep block: <name>_k0, _k1, ...)
+            parts = [v for k, v in tr.items() if k == key or k.startswith(key + '_k') or k.startswith(key + '<')]
+            if world == 1 and a.reps == 23 and parts:
+                roof['traffic'] = sum(v['hbm_bytes_per_launch'] for v in parts)
+                roof['traffic_frac_of_peak'] = roof['traffic'] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof['traffic_source'] = os.path.basename(pmc) + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, gfx950-corrected)'
+                # the counters belong to the kernel SOURCE they were collected on: tools/collect_profiles.sh stamps the profile with
+                # the sha1 of every generated fused kernel; a kernel edited since then ships its figure marked stale, not silently
+                tag_ = dominant.split('[')[-1].rstrip(']')
+                now = fused_source_hashes().get(tag_)
+                then = (tr.get('__kernel_sources__') or {}).get(tag_)
+                roof['traffic_kernel_sha1'] = then
+                roof['traffic_stale'] = (then is None) or (now != then)
+                if roof['traffic_stale']:
+                    roof['traffic_note'] = (f'PMC pass predates the current kernel source (profile: {then or "unstamped"}, tree: {now}); '
+                                            're-run tools/collect_profiles.sh')
+        except Exception:  # noqa: BLE001
+            pass
+        if any(k.endswith('@side') for k in totals):
+            roof['note'] = ("classes tagged '@side' (radial MLPs) run on a second HIP stream concurrently with the "
+                            "main-stream kernels: their event brackets overlap the others and are not exclusive time; "
+                            "avg_ms of the dominant kernel is measured with that concurrent work present")
+        roof['kernel_ms_per_step'] = {k: round(v / n_break, 4) for k, v in sorted(totals.items(), key=lambda kv: -kv[1])}
+        roof['avg_ms_source'] = 'HIP events inside the timed steps' if len(timed_dom) else 'HIP events of an untimed pass of the same kernels (native host)'
+        # whole step: SURVEY.md 8(d)'s algorithmic BYTES against the HBM peak, and the arithmetic the engine actually SCHEDULES (pruned
+        # paths, sparse Clebsch-Gordan tensors, split-precision products counted once per matrix-core product issued) against the
+        # pipes it runs on.  SURVEY's dense-CG fp32 FLOP count is kept as information only: divided into a step that runs the dense
+        # contractions as low-precision splits on the 2.5-PF pipe and prunes unread paths it gave "fractions" above 1.
+        if a.model in STEP_WORK:
+            sb, sf = (v * n_atoms for v in STEP_WORK[a.model])
+            t = dt / a.steps * world   # GPU-seconds per step
+            sched = scheduled_work(eng, graph)
+            valu_peak = VALU_F32_PEAK_TF * 1e12
+            roof['step'] = dict(bytes=sb, frac_hbm=sb / t / (HBM_PEAK_GBS * 1e9), floor_ms_hbm=sb / (HBM_PEAK_GBS * 1e9) * 1e3,
+                                mfma_flops_issued=sched['mfma'], valu_flops=sched['valu'],
+                                frac_mfma_issued=sched['mfma'] * world / t / (MFMA_BF16_PEAK_TF * 1e12),
+                                frac_valu=sched['valu'] * world / t / valu_peak,
+                                valu_peak_tflops=VALU_F32_PEAK_TF, valu_measured_tflops_by_waves_per_simd=VALU_F32_MEASURED_TF,
+                                flops_survey_dense_fp32=sf,
+                                note='bytes: SURVEY.md 8(d) per atom-step (fwd + reverse, no cache credit, radial weights not '
+                                     'materialised) over 8 TB/s.  mfma_flops_issued: every 16x16x32 / 32x32x16 product the kernels issue '
+                                     '(in-kernel W2 products x3 for f16x3, node linears and hidden radial layers x6 for bf16x6) over the '
+                                     '2.5 PFLOP/s dense f16 / bf16 peak.  valu_flops: the sparse tensor-product arithmetic as generated '
+                                     '(forward: nnz(C) FMAs + pair products per channel; reverse: Clebsch-Gordan tensor contracted with the '
+                                     'harmonics per edge, two FMAs per nonzero (a, c) pair and three per x component per channel) over '
+                                     'the 157.3 TFLOP/s fp32 vector peak (SIMD-32: a wave64 instruction issues over 2 cycles); '
+                                     'valu_measured_tflops_by_waves_per_simd = what plain v_fma_f32 streams reach on this chip by occupancy '
+                                     '(one wave issues a vector instruction every ~7.5 cycles: tools/gpu/issue_probe, '
+                                     'profiles/r05_issue_rate_probe.txt).  flops_survey_dense_fp32 = SURVEY.md 8(d)\'s dense-CG count, for '
+                                     'reference only.')
+
+        # ghost exchange of this rank per step: L-1 forward (width dx_t) + L-1 reverse exchanges + one force fold; bytes = rows
+        # sent + received; time = HIP-event brackets around the exchange calls (with the split exchange the brackets cover
+        # only the enqueue + the final wait, i.e. the part that is NOT hidden behind compute)
+        halo_ms, halo_n, halo_bytes = 0.0, 0, 0
+        if dist_mode:
+            halo_ms = sum(v for k, v in totals.items() if k.startswith('halo')) / n_break
+            rows = int(sum(len(s_) for s_ in bg.send_lists)) + int(graph.n_total - graph.n_local)
+            dims = [ls.si1.dim_out for ls in eng.spec.layers[1:]]
+            halo_n = 2 * len(dims) + 1
+            halo_bytes = rows * 4 * (2 * sum(dims) + 3)
     if rank == 0:
         res = {
             'metric': 'atom-steps/sec (energy+forces), SevenNet-0 100k-atom cell, 1/2/4/8 MI355X' if a.model == 'sevennet_0'
@@ -755,25 +799,29 @@ def main():
                        'halo_overlap': (None if not dist_mode else bool(getattr(halo, 'overlap', True))),
                        'ghost_rows_rank0': (None if not dist_mode else int(graph.n_total - graph.n_local)),
                        'decomposition_selfcheck': (None if not dist_mode else selfcheck),
-                       'halo_exposed_ms': (None if not dist_mode else round(halo_ms, 3)),   # main-stream time inside the exchange calls (start: enqueue only; finish: the wait)
-                       'halo_ms_per_step_rank0': (None if not dist_mode else round(halo_ms, 4)),
-                       'halo_exchanges_per_step': (None if not dist_mode else halo_n),
-                       'halo_bytes_per_step_rank0': (None if not dist_mode else halo_bytes),
-                       'halo_gbs_rank0': (None if not dist_mode or halo_ms <= 0 else round(halo_bytes / (halo_ms * 1e-3) / 1e9, 2)),
-                       'kernel_ms_per_step_rank0': round(sum(v for k, v in totals.items() if not k.startswith('halo')) / n_break, 3),
-                       # what the step costs beyond its kernels' own durations: dependent-dispatch gaps, the per-step input copy,
-                       # torch fill kernels (main-stream classes only: '@side' brackets overlap the others)
-                       'non_kernel_ms_per_step_rank0': round(step_ms_median - sum(v for k, v in totals.items() if not k.startswith('halo') and not k.endswith('@side')) / n_break, 3),
-                       'dispatches_per_step_rank0': int(sum(c for k, c in counts.items() if not k.startswith('halo')) / n_break),
-                       'energy': float(e_total.cpu()),
-                       # the box this line was measured on: medians over the timed region (rank 0's GPU)
-                       **tele.summary(), 'telemetry_pass_ms_per_step': round(tele_ms, 3)},
-            'roofline': roof,
+                       'energy': float(e_total.cpu())},
         }
-        if world == 1 and not dist_mode and a.brick_proxy > 1 and a.model == 'sevennet_0':
-            res['brick_proxy'] = brick_proxy(a, cfg, sd, eng, pos, cell, dev, modal, step_ms)
-        if world == 1 and not a.no_cpu_baseline:
-            res['cpu_baseline'] = cpu_baseline(cfg, sd, a.cpu_reps)
+        if a.full:
+            res['config'].update({
+                'halo_exposed_ms': (None if not dist_mode else round(halo_ms, 3)),   # main-stream time inside the exchange calls (start: enqueue only; finish: the wait)
+                'halo_ms_per_step_rank0': (None if not dist_mode else round(halo_ms, 4)),
+                'halo_exchanges_per_step': (None if not dist_mode else halo_n),
+                'halo_bytes_per_step_rank0': (None if not dist_mode else halo_bytes),
+                'halo_gbs_rank0': (None if not dist_mode or halo_ms <= 0 else round(halo_bytes / (halo_ms * 1e-3) / 1e9, 2)),
+                'kernel_ms_per_step_rank0': round(sum(v for k, v in totals.items() if not k.startswith('halo')) / n_break, 3),
+                # what the step costs beyond its kernels' own durations: dependent-dispatch gaps, the per-step input copy,
+                # torch fill kernels (main-stream classes only: '@side' brackets overlap the others)
+                'non_kernel_ms_per_step_rank0': round(step_ms_median - sum(v for k, v in totals.items() if not k.startswith('halo') and not k.endswith('@side')) / n_break, 3),
+                'dispatches_per_step_rank0': int(sum(c for k, c in counts.items() if not k.startswith('halo')) / n_break),
+                # the box this line was measured on: medians over the timed region (rank 0's GPU)
+                **tele.summary(), 'telemetry_pass_ms_per_step': round(tele_ms, 3)})
+            res['roofline'] = roof
+            if world == 1 and not dist_mode and a.brick_proxy > 1 and a.model == 'sevennet_0':
+                res['brick_proxy'] = brick_proxy(a, cfg, sd, eng, pos, cell, dev, modal, step_ms)
+            if world == 1 and not a.no_cpu_baseline:
+                res['cpu_baseline'] = cpu_baseline(cfg, sd, a.cpu_reps)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, outputs)
         # RCCL writes a version banner through C stdio, which a pipe buffers until exit: flush it now so that the JSON
         # line is the last thing on stdout
         try:

@@ -554,7 +554,7 @@ def test_bench_multi_rank_path_dry_run():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ['--reps', '6', '--steps', '1', '--warmup', '1', '--no-cpu-baseline']
+    common = ['--reps', '6', '--steps', '1', '--warmup', '1', '--full', '--no-cpu-baseline']
     env = dict(os.environ, SNET_DIST_BACKEND='gloo')
 
     def run(cmd):
@@ -589,6 +589,43 @@ def test_bench_multi_rank_path_dry_run():
     assert soak['config']['decomposition_selfcheck']['rccl_comm'] == {'nranks': 1, 'rank0_user_rank': 0}
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """`bench.py` without --full: the contract fields of the timed steps and nothing that takes a pass of its own; --dump-outputs
+    writes what the last timed step returned, and that is what the engine computes on the same seeded workload."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from bench import model_config, species_of
+    from sevennet_amd.engine import HipForceEngine, build_graph
+    from sevennet_amd.neighbor import diamond_cubic, neighbor_list
+    from sevennet_amd.synthetic import random_state_dict
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, 'bench.py', '--reps', '4', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                       cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['higher_is_better'] is True and line['unit'] == 'atom-steps/s'
+    assert line['ms_per_step'] > 0 and abs(line['value'] - line['config']['atoms'] / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']
+    assert isinstance(line['metric'], str) and isinstance(line['dtype'], str)
+    assert not {'roofline', 'cpu_baseline', 'brick_proxy'} & set(line) and 'sclk_mhz' not in line['config']
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {'energy', 'atomic_energy', 'dE_dr', 'forces', 'virial'}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+
+    cfg = model_config('sevennet_0')
+    pos, cell = diamond_cubic(5.431, (4,) * 3, 0.05, 2)
+    ei, ev, _ = neighbor_list(pos, cell, [True] * 3, cfg['cutoff'])
+    eng = HipForceEngine(cfg, random_state_dict(cfg, seed=0), device='cuda:0', fused_terms=4)
+    out = eng.compute(build_graph(species_of(cfg, len(pos)), ei, ev, device='cuda:0', num_species=eng.spec.num_species))
+    torch.cuda.synchronize()
+    assert got['energy'].shape == (1,) and got['forces'].shape == (len(pos), 3) and got['dE_dr'].shape == (ei.shape[1], 3)
+    assert abs(float(got['energy'][0]) - float(out['energy'].cpu())) <= 1e-6 * abs(float(out['energy'].cpu()))
+    for k in ('atomic_energy', 'dE_dr', 'forces', 'virial'):
+        want = out[k].cpu().numpy()
+        assert np.abs(got[k] - want).max() <= 1e-5 * np.abs(want).max(), (k, np.abs(got[k] - want).max(), np.abs(want).max())
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two GPUs: real RCCL at world size 2')
 def test_bench_two_ranks_real_rccl():
     """the day a box has two GPUs this runs `bench.py --gpus 2` on REAL RCCL (one rank per GPU, the library's own
@@ -599,7 +636,7 @@ def test_bench_two_ranks_real_rccl():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ['--reps', '8', '--steps', '2', '--warmup', '1', '--no-cpu-baseline']
+    common = ['--reps', '8', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline']
 
     def run(cmd):
         r = subprocess.run(cmd, cwd=root, env=dict(os.environ), capture_output=True, text=True, timeout=900)

@@ -1,25 +1,33 @@
-"""CPU, build container only: pin the LAMMPS MOCK (tests/lammps_mock/) to LAMMPS itself.
+"""CPU: pin the LAMMPS MOCK (tests/lammps_mock/) to LAMMPS itself.
 
 The glue (lammps/pair_e3gnn_hip.cpp, pair_d3_hip.cpp) is compiled and executed against a mock this repository wrote, so a signature
-that differs from LAMMPS would compile here and fail for the first user.  No LAMMPS tree exists in the image, but the reference
+that differs from LAMMPS would compile here and fail for the first user.  No LAMMPS tree is at hand, but the reference
 holds stock LAMMPS text and code written against the target release (stable_2Aug2023_update3): the vendored
 sevenn/pair_e3gnn/comm_brick.{h,cpp} (LAMMPS' own CommBrick) and the reference's pair styles pair_e3gnn.cpp,
-pair_e3gnn_parallel.cpp, pair_d3.cu.  This test extracts, at test time and from the files where they lie under /root/reference
-(nothing is copied), every LAMMPS call and member access those sources make, and checks:
+pair_e3gnn_parallel.cpp, pair_d3.cu.  oracle/tools/make_golden_lammps_calls.py extracted from them, with the parser below, every
+LAMMPS call and member access those sources make (names and argument counts only: tests/golden/lammps_reference_calls.json), and
+this test checks:
   * the mock declares CommBrick's entry points and the pair-side hooks with the argument lists stock LAMMPS calls them with;
   * every LAMMPS call / member the GLUE uses is one the reference's sources use too, with the same number of arguments --
-    whatever is not is exactly the list INTEGRATION.md publishes as unverified.
-Skipped where /root/reference is absent (the GPU box)."""
+    whatever is not is exactly the list INTEGRATION.md publishes as unverified."""
+import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference/sevenn/pair_e3gnn'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='needs the reference tree (build container)')
+GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'lammps_reference_calls.json')
 
 OBJECTS = ('memory', 'error', 'atom', 'comm', 'neighbor', 'domain', 'force', 'list', 'utils', 'NeighConst')
+# unqualified members inherited from LAMMPS' Pair that the mock declares (the fixture records which of them the reference uses)
+PAIR_MEMBERS = ('eng_vdwl', 'eng_coul', 'virial', 'eatom', 'vatom', 'comm_forward', 'comm_reverse', 'single_enable', 'restartinfo',
+                'one_coeff', 'manybody_flag', 'no_virial_fdotr_compute', 'list', 'allocated', 'setflag', 'cutsq', 'map', 'eflag_either',
+                'eflag_global', 'eflag_atom', 'vflag_either', 'vflag_global', 'vflag_atom', 'ev_setup', 'evflag', 'vflag_fdotr',
+                'maxeatom', 'maxvatom')
+
+
+def _reference():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _strip(text):
@@ -55,40 +63,20 @@ def lammps_uses(text):
     return out
 
 
-def _read(*names, base=REF):
+def _read(*names, base):
     return '\n'.join(open(os.path.join(base, n)).read() for n in names)
 
 
 def test_comm_brick_entry_points_and_pair_hooks_match_stock_lammps():
-    """stock LAMMPS (vendored comm_brick.{h,cpp}): Comm::forward_comm(Pair *) / reverse_comm(Pair *) and the four pair-side hooks
+    """stock LAMMPS (the reference's vendored CommBrick): Comm::forward_comm(Pair *) / reverse_comm(Pair *) and the four pair-side hooks
     with the arguments CommBrick passes them; the mock's Comm / Pair must declare exactly those"""
-    h, c = _strip(_read('comm_brick.h')), _strip(_read('comm_brick.cpp'))
-    assert re.search(r'void\s+forward_comm\s*\(\s*class\s+Pair\s*\*\s*\)\s*override', h)
-    assert re.search(r'void\s+reverse_comm\s*\(\s*class\s+Pair\s*\*\s*\)\s*override', h)
-    calls = {}
-    for m in re.finditer(r'\bpair\s*->\s*(\w+)\s*\(', c):
-        calls.setdefault(m.group(1), set()).add(_args(c, m.end() - 1))
+    ref = _reference()
+    assert {'forward_comm', 'reverse_comm'} <= set(ref['comm_overrides_taking_pair'])
+    calls = {fn: set(n) for fn, n in ref['pair_calls_from_comm'].items()}
     assert calls['pack_forward_comm'] == {5} and calls['unpack_forward_comm'] == {3}
     assert calls['pack_reverse_comm'] == {3} and calls['unpack_reverse_comm'] == {3}
-    # argument TYPES at the stock call sites, from CommBrick's own member declarations (comm_brick.h): indexed once, an
-    # `int *` member is an int and an `int **` member an int *; the buffers are double *
-    def member_type(name):
-        m = re.search(r'\b(int|double)\s*([^;]*?)(\*{0,2})\s*' + name + r'\b[^;]*;', h)
-        if m is None:   # a local of the calling function (double *buf)
-            m = re.search(r'\b(int|double)\s*(\*{0,2})\s*' + name + r'\s*;', c)
-        assert m, name
-        decl = re.search(r'(\*{0,2})\s*' + name + r'\b', m.group(0)).group(1)
-        return m.group(1), len(decl)
-
-    def arg_type(expr):
-        expr = expr.strip()
-        base, idx = re.match(r'(\w+)((?:\[[^\]]*\])*)$', expr).groups()
-        t, stars = member_type(base)
-        stars -= idx.count('[')
-        return t + (' ' + '*' * stars if stars else '')
-    sites = {fn: re.search(r'pair\s*->\s*' + fn + r'\s*\(([^;]*?)\)\s*;', c).group(1).split(',')
-             for fn in ('pack_forward_comm', 'unpack_forward_comm', 'pack_reverse_comm', 'unpack_reverse_comm')}
-    want = {fn: ', '.join(arg_type(a) for a in args) for fn, args in sites.items()}
+    # argument TYPES at the stock call sites, from CommBrick's own member declarations (the generator's member_type / arg_type)
+    want = ref['pair_hook_arg_types']
     assert want == {'pack_forward_comm': 'int, int *, double *, int, int *', 'unpack_forward_comm': 'int, int, double *',
                     'pack_reverse_comm': 'int, int, double *', 'unpack_reverse_comm': 'int, int *, double *'}, want
     norm = lambda s_: re.sub(r'\s+', ' ', re.sub(r'\s*\*\s*', ' *', s_)).strip()  # noqa: E731
@@ -112,11 +100,10 @@ def _unverified_block():
 
 
 def test_every_lammps_call_of_the_glue_is_one_the_reference_makes():
-    ref = lammps_uses(_read('pair_e3gnn.cpp', 'pair_e3gnn_parallel.cpp', 'pair_d3.cu', 'pair_e3gnn.h', 'pair_e3gnn_parallel.h', 'pair_d3.h',
-                            'comm_brick.cpp'))
+    ref = {(o, n): set(counts) for o, n, counts in _reference()['lammps_uses']}
     # stock Comm entry points declared in the vendored header count as LAMMPS text too (the reference itself calls its own overloads)
-    for m in re.finditer(r'\bvoid\s+(\w+)\s*\(([^)]*)\)\s*override', _strip(_read('comm_brick.h'))):
-        ref.setdefault(('comm', m.group(1)), set()).add(len([a for a in m.group(2).split(',') if a.strip()]))
+    for name, counts in _reference()['comm_overrides'].items():
+        ref.setdefault(('comm', name), set()).update(counts)
     glue = lammps_uses(_read('pair_e3gnn_hip.cpp', 'pair_e3gnn_hip.h', 'pair_d3_hip.cpp', 'pair_d3_hip.h', base=os.path.join(ROOT, 'lammps')))
     assert len(glue) >= 20 and ('memory', 'create') in glue and ('neighbor', 'add_request') in glue
     unverified, arity = set(), []
@@ -144,15 +131,14 @@ def test_pair_base_members_the_glue_uses_are_the_ones_the_reference_uses():
     only those the reference's pair styles use too"""
     mock = _strip(_read('pair.h', base=os.path.join(ROOT, 'tests', 'lammps_mock')))
     body = mock[mock.index('class Pair'):]
-    members = ['eng_vdwl', 'eng_coul', 'virial', 'eatom', 'vatom', 'comm_forward', 'comm_reverse', 'single_enable', 'restartinfo', 'one_coeff',
-               'manybody_flag', 'no_virial_fdotr_compute', 'list', 'allocated', 'setflag', 'cutsq', 'map', 'eflag_either', 'eflag_global',
-               'eflag_atom', 'vflag_either', 'vflag_global', 'vflag_atom', 'ev_setup', 'evflag', 'vflag_fdotr', 'maxeatom', 'maxvatom']
+    members = PAIR_MEMBERS
     for m in members:
         assert re.search(r'\b' + m + r'\b', body), m                 # the list above is what the mock's Pair declares
-    ref = _strip(_read('pair_e3gnn.cpp', 'pair_e3gnn_parallel.cpp', 'pair_d3.cu'))
+    ref = _reference()
+    assert ref['pair_members_checked'] == list(members), 'the member list changed: regenerate the fixture'
     glue = _strip(_read('pair_e3gnn_hip.cpp', 'pair_d3_hip.cpp', base=os.path.join(ROOT, 'lammps')))
     used = {m for m in members if re.search(r'(?<![\w>.])' + m + r'\b', glue)}
     assert {'eng_vdwl', 'virial', 'setflag', 'cutsq', 'ev_setup', 'evflag', 'vflag_fdotr'} <= used
-    missing = {'Pair::' + m for m in used if not re.search(r'(?<![\w>.])' + m + r'\b', ref)}
+    missing = {'Pair::' + m for m in used if m not in ref['pair_members_used']}
     # (the reference adds its energy / virial unconditionally; the glue honours LAMMPS' global flags)
     assert missing == {u for u in _unverified_block() if u.startswith('Pair::')}, sorted(missing)

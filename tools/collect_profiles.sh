@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o r -- $BENCH > $OUT/${TAG}_stats.log 2>&1
 # counter passes with the radial MLPs on the main stream: TCC counters are device-wide, concurrent kernels
 # of a second stream would be charged to whichever dispatch is being sampled
@@ -35,6 +35,6 @@ json.dump(d, open(p, 'w'), indent=1)
 PY
 # the bench line itself, with the fresh traffic file visible to bench.py
 cp $OUT/${TAG}_pmc_hbm_traffic.json profiles/${TAG}_pmc_hbm_traffic.json
-python bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
+python bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/${TAG}_bench_n1.err
 rm -rf $OUT/${TAG}_fetch $OUT/${TAG}_write $OUT/${TAG}_stats $OUT/${TAG}_mfma   # raw traces are large; summaries stay
 tail -c 600 $OUT/${TAG}_bench_n1.json

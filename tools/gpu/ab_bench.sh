@@ -4,7 +4,7 @@
 for rep in 1 2; do
 for v in head new; do
 if [ $v = head ]; then export SNET_HIP_LIB=$PWD/exp/libx_head.so; else unset SNET_HIP_LIB; fi
-timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 k=r['kernel_ms_per_step']

@@ -4,7 +4,7 @@
 for rep in 1 2; do
 for v in tree "$@"; do
   if [ $v = tree ]; then unset SNET_HIP_LIB; else export SNET_HIP_LIB=$PWD/exp/libx_$v.so; fi
-  timeout 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernel_ms_per_step']
 keys=('conv_bwd_fused[22d6a77ad5ac]','conv_fwd_fused[22d6a77ad5ac]','conv_bwd_node[segment_sum]','node_linear_fwd','node_linear_bwd')
