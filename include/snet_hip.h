@@ -355,6 +355,23 @@ int snet_edge_force(const float *g_vec, const float *edge_vec, const int32_t *ro
                     const int32_t *eperm, int64_t n_nodes, int64_t n_edges, float *forces, float *virial_atom,
                     double *virial_total, void *stream);
 
+/* ---- batched evaluation: per-system fp64 reductions ------------------------
+ * The atoms of B systems are contiguous segments seg_ptr[B+1] (device int32, seg_ptr[0] = 0, seg_ptr[B] = n_nodes) of
+ * one graph whose edges never cross systems.  The variants below compute exactly what their single-total namesakes
+ * compute per atom, keep the fp64 per-atom values and sum them per segment in a fixed order (AtomReduce per graph,
+ * sevenn/nn/linear.py:127-141; the per-graph virial scatter of force_output.py:213-228):
+ *   energy_seg[B] / virial_seg[B,6] (device double), and *_total (device double, may be NULL) = their fixed-order sum.
+ * Deterministic: two runs give bit-identical results.  A segment may hold one atom without edges.  */
+int snet_readout_energy_seg(const float *x, int64_t n_nodes, int32_t dim, const double *v, double c, const int32_t *types,
+                            const float *scale, const float *shift, int32_t n_scale, const int32_t *seg_ptr, int32_t n_seg,
+                            float *e_atom, double *energy_seg, double *energy_total, void *stream);
+int snet_rescale_reduce_seg(const float *e_scaled, const int32_t *types, const float *scale, const float *shift,
+                            int32_t n_scale, int64_t n_nodes, const int32_t *seg_ptr, int32_t n_seg, float *e_atom,
+                            double *energy_seg, double *energy_total, void *stream);
+int snet_edge_force_seg(const float *g_vec, const float *edge_vec, const int32_t *row_ptr, const int32_t *col_ptr,
+                        const int32_t *eperm, int64_t n_nodes, int64_t n_edges, const int32_t *seg_ptr, int32_t n_seg,
+                        float *forces, float *virial_atom, double *virial_seg, double *virial_total, void *stream);
+
 /* ---- a12: halo pack / unpack ---------------------------------------------
  * replaces PairE3GNNParallel::pack_forward_comm_gnn / unpack_reverse_comm_gnn,
  * pair_e3gnn_parallel.cpp:747-911 (index_select / scatter / scatter-add).
@@ -385,6 +402,20 @@ int snet_nl_fill(const double *cell_host, double cutoff, const int32_t *pbc_host
                  const double *wpos, const int32_t *wrap, const int32_t *cell_id, const int32_t *order,
                  const int32_t *bin_start, int64_t n_atoms, const int32_t *row_ptr, int32_t *src, int32_t *center,
                  float *edge_vec, int32_t *shifts, void *stream);
+
+/* Batched neighbor list of B small systems (one count launch, one fill launch): atoms of system s are rows
+ * [atom_ptr[s], atom_ptr[s+1]) of pos[n_atoms,3] (fp64); cells[B,9] (row-major lattice vectors, fp64) and pbc[B,3]
+ * (int32) per system, all on the device.  Same conventions and CSR-by-center output as snet_nl_fill (every ordered pair
+ * within the cutoff, no self edge, edge_vec = r_j - r_i + S.cell in fp64 stored as fp32, open axes neither wrapped nor
+ * imaged, a zero cell row of an open axis padded); indices are global, shifts (may be NULL) relative to the given
+ * positions.  One lane per center atom over the atoms of its own system: O(n_s^2) work per system.  A system whose cell is
+ * singular after padding, or thinner than 1/64 of the cutoff along a periodic axis, gets no edges (the host routes it
+ * elsewhere).  snet_batch_nl_count writes count[n_atoms]; the caller scans it into row_ptr for snet_batch_nl_fill.  */
+int snet_batch_nl_count(const double *pos, const int32_t *atom_ptr, int32_t n_sys, const double *cells, const int32_t *pbc,
+                        int64_t n_atoms, double cutoff, int32_t *count, void *stream);
+int snet_batch_nl_fill(const double *pos, const int32_t *atom_ptr, int32_t n_sys, const double *cells, const int32_t *pbc,
+                       int64_t n_atoms, double cutoff, const int32_t *row_ptr, int32_t *src, int32_t *center,
+                       float *edge_vec, int32_t *shifts, void *stream);
 
 /* ---- whole-model sequencer ------------------------------------------------------------------
  * replaces, for a native (C++) host, `model.forward(input_dict)` + `torch::autograd::grad(...)` of

@@ -114,6 +114,15 @@ SIGNATURES = {
     'snet_readout_grad': (C.c_int, [c_f64p, C.c_int32, c_i32p, c_f32p, C.c_int32, C.c_int64, c_f32p, c_stream]),
     'snet_edge_force': (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, c_f32p, c_f32p,
                                   c_f64p, c_stream]),
+    'snet_readout_energy_seg': (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f64p, C.c_double, c_i32p, c_f32p, c_f32p, C.c_int32,
+                                          c_i32p, C.c_int32, c_f32p, c_f64p, c_f64p, c_stream]),
+    'snet_rescale_reduce_seg': (C.c_int, [c_f32p, c_i32p, c_f32p, c_f32p, C.c_int32, C.c_int64, c_i32p, C.c_int32, c_f32p, c_f64p,
+                                          c_f64p, c_stream]),
+    'snet_edge_force_seg': (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, c_i32p, C.c_int32, c_f32p,
+                                      c_f32p, c_f64p, c_f64p, c_stream]),
+    'snet_batch_nl_count': (C.c_int, [C.c_void_p, c_i32p, C.c_int32, C.c_void_p, c_i32p, C.c_int64, C.c_double, c_i32p, c_stream]),
+    'snet_batch_nl_fill': (C.c_int, [C.c_void_p, c_i32p, C.c_int32, C.c_void_p, c_i32p, C.c_int64, C.c_double, c_i32p, c_i32p,
+                                     c_i32p, c_f32p, c_i32p, c_stream]),
     'snet_nl_grid': (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     'snet_nl_bin': (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p, C.c_int64,
                               C.c_void_p, c_i32p, c_i32p, c_stream]),

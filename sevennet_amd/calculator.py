@@ -18,7 +18,7 @@ from __future__ import annotations
 import os
 import pathlib
 import warnings
-from typing import Any, Dict, Optional, Union
+from typing import Any, Dict, List, Optional, Union
 
 import numpy as np
 import torch
@@ -274,6 +274,48 @@ class SevenNetCalculator(Calculator):
         if self.compute_atomic_virial:
             res['stresses'] = out['atomic_virial'].cpu().numpy()
         return res
+
+    def compute_many(self, numbers_list, positions_list, cells, pbcs) -> List[Dict[str, Any]]:
+        """`compute` for B structures in ONE engine call (sevennet_amd.batch): one results dict per system, in the given
+        order, with the keys, units, Voigt order and stress sign of `compute`.  cells[B,3,3], pbcs[B,3] (or one [3])."""
+        from .batch import build_batch_graph, virial_to_stress
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        types_list = []
+        for numbers in numbers_list:
+            numbers = np.asarray(numbers, np.int64).reshape(-1)
+            types = self._z2type[np.clip(numbers, 0, len(self._z2type) - 1)]
+            if ((types < 0) | (numbers < 0) | (numbers >= len(self._z2type))).any():
+                bad = sorted(set(numbers[(types < 0) | (numbers < 0) | (numbers >= len(self._z2type))].tolist()))
+                raise ValueError(f'Model do not know atomic number: {bad[0]}, (knows: {list(self.type_map.keys())})')
+            types_list.append(types)
+        ns = self.model.spec.num_species
+        g = build_batch_graph(types_list, list(positions_list), cells, pbcs, self.cutoff, ns, device=str(self.device),
+                              species_rows=self.model.needs_species_rows)
+        out = self.model.compute(g, want_atomic_virial=self.compute_atomic_virial)
+        sp = g.seg_ptr_host
+        e_sys = out['energy_per_system'].cpu().numpy()
+        stress = virial_to_stress(out['virial_per_system'].cpu().numpy(), np.asarray(cells, np.float64).reshape(-1, 3, 3))
+        energies = out['atomic_energy'].cpu().numpy().astype(np.float64)
+        forces = out['forces'].cpu().numpy().astype(np.float64)
+        n_edges = np.diff(g.row_ptr[torch.as_tensor(sp).to(g.row_ptr.device)].cpu().numpy())
+        atomic_virial = out['atomic_virial'].cpu().numpy() if self.compute_atomic_virial else None
+        results = []
+        for b in range(len(sp) - 1):
+            a0, a1 = int(sp[b]), int(sp[b + 1])
+            res: Dict[str, Any] = {'free_energy': float(e_sys[b]), 'energy': float(e_sys[b]), 'energies': energies[a0:a1],
+                                   'forces': forces[a0:a1], 'stress': stress[b], 'num_edges': int(n_edges[b])}
+            if atomic_virial is not None:
+                res['stresses'] = atomic_virial[a0:a1]
+            results.append(res)
+        return results
+
+    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
+        """`compute_many` over ASE-like objects (anything with get_atomic_numbers / get_positions / get_cell / get_pbc)"""
+        atoms_list = list(atoms_list)
+        return self.compute_many([a.get_atomic_numbers() for a in atoms_list], [a.get_positions() for a in atoms_list],
+                                 np.array([np.array(a.get_cell(), np.float64).reshape(3, 3) for a in atoms_list]).reshape(-1, 3, 3),
+                                 np.array([np.asarray(a.get_pbc(), bool).reshape(3) for a in atoms_list]).reshape(-1, 3))
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         Calculator.calculate(self, atoms, properties, system_changes)

@@ -837,7 +837,9 @@ extern "C" int snet_radial_mlp_hidden_fwd_layers(const snet_mlp_plan *const *pla
   bool silu = true;
   for (int l = 0; l < n_layers; ++l) {
     const snet_mlp_plan *p = plans[l];
-    SNET_REQUIRE(p != nullptr && h2[l] != nullptr, "snet_radial_mlp_hidden_fwd_layers: null plan / output");
+    SNET_REQUIRE(p != nullptr, "snet_radial_mlp_hidden_fwd_layers: null plan");
+    // a graph without edges hands over empty outputs (null data pointers): nothing is written, only the plans are checked
+    SNET_REQUIRE(E <= 0 || h2[l] != nullptr, "snet_radial_mlp_hidden_fwd_layers: null output");
     SNET_REQUIRE(p->mode == 1, "snet_radial_mlp_hidden_fwd_layers: split-precision plans only (mode 1)");
     SNET_REQUIRE(p->nb == plans[0]->nb, "snet_radial_mlp_hidden_fwd_layers: the layers must share the edge embedding (same n_basis)");
     P.W0[l] = p->W0; P.W1A[l] = p->W1A; P.h2[l] = h2[l]; P.cst[l] = p->cst; P.act[l] = p->act;

@@ -71,6 +71,10 @@ class Graph:
     n_interior: int = 0
     _tile_split: Optional[tuple] = None
     _tiles_packed: Optional[tuple] = None
+    # batch of B systems (sevennet_amd.batch): atoms of system b are the rows [seg_ptr[b], seg_ptr[b+1]); edges never cross
+    # systems.  Device int32 [B+1] and its host copy; None = one system
+    seg_ptr: Optional[torch.Tensor] = None
+    seg_ptr_host: Optional[np.ndarray] = None
 
     def by_source(self, lib, stream):
         """(center[eperm], w_row[eperm]) as int32 arrays, built on first use (w_row None: the edge's own row, eperm)"""
@@ -616,6 +620,8 @@ class HipForceEngine:
         lib, sp = self.lib, self.spec
         if self.needs_species_rows and g.species_rows is None:
             raise ValueError('graph was built without num_species but the model has a per-species self-connection')
+        if g.seg_ptr is not None and (halo is not None or g.n_total != g.n_local):
+            raise ValueError('a batch of systems (Graph.seg_ptr) cannot be combined with a halo decomposition')
         with torch.cuda.device(self.dev):
             c = self._begin(g, halo, keep)            # edge embedding, radial-weight streams, hidden radial layers
             x = self._forward_layers(c)                # interaction layers; what the reverse pass needs goes to c.saved
@@ -796,6 +802,7 @@ class HipForceEngine:
         lib, sp, g, st, N = self.lib, self.spec, c.g, c.st, c.N
         e_atom = self._new(N)
         energy = torch.empty(1, dtype=torch.float64, device=self.dev)
+        c.e_sys = None if g.seg_ptr is None else torch.empty(len(g.seg_ptr_host) - 1, dtype=torch.float64, device=self.dev)
         d_ro = sp.readout1.dim_in
         if self.ro_fcn is not None:   # readout_as_fcn: x -> act(x W0) cst -> ... -> e, then its reverse (nn/linear.py:145-180)
             F = self.ro_fcn
@@ -808,8 +815,7 @@ class HipForceEngine:
                     a = self._new(N, d[i + 1])
                     _lib.check(lib.snet_act_fwd(_ptr(z), _ptr(a), z.numel(), F.act, F.cst, st), 'snet_act_fwd')
                     zs.append(z)
-            _lib.check(lib.snet_rescale_reduce(_ptr(z), _ptr(g.types), _ptr(self.scale), _ptr(self.shift),
-                                               self.n_scale, N, _ptr(e_atom), _ptr(energy), st), 'snet_rescale_reduce')
+            self._rescale_reduce(c, z, e_atom, energy)
             gz = self._new(N, 1)
             if self.n_scale > 1:
                 _lib.check(lib.snet_embed_rows(_ptr(self.scale), _ptr(g.types), _ptr(gz), N, 1, st), 'snet_embed_rows')
@@ -823,16 +829,20 @@ class HipForceEngine:
                 gz = ga
             g_x = gz
         elif self.ro_v is not None:   # folded readout: fp64 dot product + rescale + energy sum in one pass
-            _lib.check(lib.snet_readout_energy(_ptr(x), N, d_ro, _ptr(self.ro_v), self.ro_c, _ptr(g.types), _ptr(self.scale),
-                                               _ptr(self.shift), self.n_scale, _ptr(e_atom), _ptr(energy), st), 'snet_readout_energy')
+            if c.e_sys is None:
+                _lib.check(lib.snet_readout_energy(_ptr(x), N, d_ro, _ptr(self.ro_v), self.ro_c, _ptr(g.types), _ptr(self.scale),
+                                                   _ptr(self.shift), self.n_scale, _ptr(e_atom), _ptr(energy), st), 'snet_readout_energy')
+            else:   # a batch: the same, summed per system
+                _lib.check(lib.snet_readout_energy_seg(_ptr(x), N, d_ro, _ptr(self.ro_v), self.ro_c, _ptr(g.types), _ptr(self.scale),
+                                                       _ptr(self.shift), self.n_scale, _ptr(g.seg_ptr), c.e_sys.numel(), _ptr(e_atom),
+                                                       _ptr(c.e_sys), _ptr(energy), st), 'snet_readout_energy_seg')
             g_x = self._new(N, d_ro)
             _lib.check(lib.snet_readout_grad(_ptr(self.ro_v), d_ro, _ptr(g.types), _ptr(self.scale), self.n_scale, N, _ptr(g_x),
                                              st), 'snet_readout_grad')
         else:
             h1 = self._linear(self.ro1, x, N, g)
             e_sc = self._linear(self.ro2, h1, N, g)
-            _lib.check(lib.snet_rescale_reduce(_ptr(e_sc), _ptr(g.types), _ptr(self.scale), _ptr(self.shift),
-                                               self.n_scale, N, _ptr(e_atom), _ptr(energy), st), 'snet_rescale_reduce')
+            self._rescale_reduce(c, e_sc, e_atom, energy)
             # ---------------- reverse pass: dE/d(e_scaled) = scale[type]
             g_e = self._new(N, 1)
             if self.n_scale > 1:
@@ -842,6 +852,17 @@ class HipForceEngine:
             g_h1 = self._linear_T(self.ro2, g_e, N, g)
             g_x = self._linear_T(self.ro1, g_h1, N, g)
         return e_atom, energy, g_x
+
+    def _rescale_reduce(self, c, e_sc, e_atom, energy):
+        """atomic energies from the readout's output and their fp64 sum (per system as well when the graph is a batch)"""
+        lib, g, st, N = self.lib, c.g, c.st, c.N
+        if c.e_sys is None:
+            _lib.check(lib.snet_rescale_reduce(_ptr(e_sc), _ptr(g.types), _ptr(self.scale), _ptr(self.shift),
+                                               self.n_scale, N, _ptr(e_atom), _ptr(energy), st), 'snet_rescale_reduce')
+        else:
+            _lib.check(lib.snet_rescale_reduce_seg(_ptr(e_sc), _ptr(g.types), _ptr(self.scale), _ptr(self.shift), self.n_scale, N,
+                                                   _ptr(g.seg_ptr), c.e_sys.numel(), _ptr(e_atom), _ptr(c.e_sys), _ptr(energy), st),
+                       'snet_rescale_reduce_seg')
 
     def _reverse_layers(self, c, g_x):
         """reverse pass through the interaction layers and the edge embedding; returns g_vec[E, 3] = dE/d(edge vector)"""
@@ -1012,9 +1033,16 @@ class HipForceEngine:
         forces = self._new(NT, 3)
         vir_atom = self._new(NT, 6) if want_atomic_virial else None
         virial = torch.empty(6, dtype=torch.float64, device=self.dev)
-        _lib.check(lib.snet_edge_force(_ptr(g_vec), _ptr(g.edge_vec), _ptr(g.row_ptr), _ptr(g.col_ptr),
-                                       _ptr(g.eperm), NT, E, _ptr(forces), _ptr(vir_atom), _ptr(virial), st),
-                   'snet_edge_force')
+        vir_sys = None
+        if c.e_sys is None:
+            _lib.check(lib.snet_edge_force(_ptr(g_vec), _ptr(g.edge_vec), _ptr(g.row_ptr), _ptr(g.col_ptr),
+                                           _ptr(g.eperm), NT, E, _ptr(forces), _ptr(vir_atom), _ptr(virial), st),
+                       'snet_edge_force')
+        else:   # a batch: the virial per system beside the total
+            vir_sys = torch.empty(c.e_sys.numel(), 6, dtype=torch.float64, device=self.dev)
+            _lib.check(lib.snet_edge_force_seg(_ptr(g_vec), _ptr(g.edge_vec), _ptr(g.row_ptr), _ptr(g.col_ptr), _ptr(g.eperm), NT, E,
+                                               _ptr(g.seg_ptr), c.e_sys.numel(), _ptr(forces), _ptr(vir_atom), _ptr(vir_sys),
+                                               _ptr(virial), st), 'snet_edge_force_seg')
         if halo is not None:  # fold ghost-atom force (and atomic virial) contributions into their owners: ONE exchange
             with _Span(self, 'halo_rev'):
                 if vir_atom is None:
@@ -1030,6 +1058,8 @@ class HipForceEngine:
         out = dict(energy=energy, atomic_energy=e_atom, dE_dr=g_vec, forces=forces[:N], virial=virial)
         if vir_atom is not None:
             out['atomic_virial'] = vir_atom[:N]
+        if vir_sys is not None:
+            out['energy_per_system'], out['virial_per_system'] = c.e_sys, vir_sys
         if keep:
             out['inter'] = inter
         return out
