@@ -586,7 +586,13 @@ int snet_md_compute(snet_md_host *host, int32_t inum, const int32_t *ilist, cons
  *   snet_d3_set_tables  r0ab[94*94] (A), c6ab[n_c6*5] (C6, Z_i + 100 ref_i, Z_j + 100 ref_j, CN_i, CN_j), r2r4[94], rcov[94]
  *   snet_d3_settings    damping 0 = damp_zero, 1 = damp_bj; func5 = (s6, rs6, s18, rs18, alp) of the functional
  *   snet_d3_set_cell    cell[9]: lattice vectors as rows (any orientation: no LAMMPS-style rotation needed), pbc[3]
- *   snet_d3_stress      [9] = dE/d(strain) / volume, row-major symmetric (ASE sign convention)                          */
+ *   snet_d3_stress      [9] = dE/d(strain) / volume, row-major symmetric (ASE sign convention)
+ * Batches: snet_d3_compute_batch evaluates n_sys systems -- atoms [atom_ptr[s], atom_ptr[s+1]) of the flat arrays, cell
+ * cells[9 s ..] (rows = lattice vectors, A; molecules need a box, as for snet_d3_compute), pbc[3 s ..] -- in one set of
+ * three launches, with the tables and settings of the handle (snet_d3_set_atoms / _set_cell are not used).  Every system's
+ * results equal those of snet_d3_compute on it bit for bit.  Outputs are caller-owned host buffers: energy[n_sys] (eV),
+ * forces[3 N] (eV/A), stress[9 n_sys] (as snet_d3_stress, per system), cn[N].  Errors name the system ("system 3: ...");
+ * at most 2^31 - 1 atoms in total.  Synchronises `stream` before it returns.                                           */
 typedef struct snet_d3 snet_d3;
 int snet_d3_create(snet_d3 **out);
 void snet_d3_destroy(snet_d3 *d3);
@@ -595,6 +601,10 @@ int snet_d3_settings(snet_d3 *d3, double vdw_cutoff_au2, double cn_cutoff_au2, i
 int snet_d3_set_atoms(snet_d3 *d3, int32_t n, const int32_t *atomic_numbers, const double *positions);
 int snet_d3_set_cell(snet_d3 *d3, const double *cell9, const int32_t *pbc3);
 int snet_d3_compute(snet_d3 *d3, void *stream);
+int snet_d3_compute_batch(snet_d3 *d3, int32_t n_sys, const int64_t *atom_ptr /*[n_sys+1]*/, const int32_t *atomic_numbers /*[N]*/,
+                          const double *positions /*[N*3], A*/, const double *cells /*[n_sys*9], A*/, const int32_t *pbc /*[n_sys*3]*/,
+                          double *energy /*[n_sys], eV*/, double *forces /*[N*3], eV/A*/, double *stress /*[n_sys*9], eV/A^3*/,
+                          double *cn /*[N]*/, void *stream);
 double snet_d3_energy(const snet_d3 *d3);
 const double *snet_d3_forces(const snet_d3 *d3);
 const double *snet_d3_stress(const snet_d3 *d3);

@@ -176,6 +176,8 @@ SIGNATURES = {
     'snet_d3_set_atoms': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'snet_d3_set_cell': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'snet_d3_compute': (C.c_int, [C.c_void_p, c_stream]),
+    'snet_d3_compute_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream]),
     'snet_d3_energy': (C.c_double, [C.c_void_p]),
     'snet_d3_forces': (C.POINTER(C.c_double), [C.c_void_p]),
     'snet_d3_stress': (C.POINTER(C.c_double), [C.c_void_p]),

@@ -11,7 +11,11 @@
 //   * fp64 throughout (the reference's known answers carry float32 summation error of a few 1e-5 relative on lattice
 //     sums of 1e5 translations; MI355X vector fp64 runs at half the fp32 rate);
 //   * flat device tables: wrapped positions [n,3] (bohr), translations [T,3], per-pair C6 and dC6/dCN_i [n,n], the
-//     reference-C6 grid of the elements present [nt,nt,5,5,3].
+//     reference-C6 grid of the elements present [nt,nt,5,5,3];
+//   * batches: the grid covers the atoms of B systems; workgroup i reads its system's D3Sys (atom range, the offsets,
+//     counts and zero-translation indices of its two translation lists, t_chunks) and offsets every per-atom pointer to
+//     that system's first atom, so its traversal is the single-system one: a batch equals B single calls bit for bit
+//     (snet_d3_compute is the B = 1 case of the same routine).
 // Units inside: bohr / hartree (0.52917726 A, 27.21138505 eV); outputs eV, eV/A, eV/A^3.
 #include <cmath>
 #include <cstring>
@@ -31,6 +35,13 @@ struct Func {
   int damping;  // 0 zero, 1 Becke-Johnson
 };
 
+// one system of a batch: atoms [a0, a0 + n), vdW translations [tv0, tv0 + Tv) and CN translations [tc0, tc0 + Tc) of the
+// concatenated lists (zv, zc: the index of the zero translation within each), t_chunks of d3_pair_kernel
+struct D3Sys {
+  int64_t a0, tv0, tc0;
+  int32_t n, Tv, zv, Tc, zc, t_chunks;
+};
+
 __device__ __forceinline__ double block_sum(double v, double *sh) {
   // fixed-order tree over the workgroup's 256 threads (deterministic)
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -42,11 +53,13 @@ __device__ __forceinline__ double block_sum(double v, double *sh) {
 }
 
 // CN_i = sum over (j, tau) != (i, 0) with r^2 <= cn_cut of 1 / (1 + exp(-K1 ((rcov_i + rcov_j) / r - 1)))
-__global__ __launch_bounds__(NTH) void d3_cn_kernel(const double *__restrict__ x, const double *__restrict__ tau, int n,
-                                                    int T, int t_zero, const double *__restrict__ rcov, double cn_cut,
-                                                    double *__restrict__ cn) {
+__global__ __launch_bounds__(NTH) void d3_cn_kernel(const D3Sys *__restrict__ sys, const int32_t *__restrict__ sys_of,
+                                                    const double *__restrict__ x, const double *__restrict__ tau,
+                                                    const double *__restrict__ rcov, double cn_cut, double *__restrict__ cn) {
   __shared__ double sh[4];
-  const int i = blockIdx.x;
+  const D3Sys S = sys[sys_of[blockIdx.x]];
+  const int i = (int)(blockIdx.x - S.a0), n = S.n, T = S.Tc, t_zero = S.zc;
+  x += 3 * S.a0; tau += 3 * S.tc0; rcov += S.a0; cn += S.a0;
   const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], rci = rcov[i];
   double acc = 0.0;
   const int64_t total = (int64_t)n * T;
@@ -109,15 +122,19 @@ __device__ __forceinline__ void d3_phi(const Func &F, double r2, double r42, dou
 
 // row i of the two-body sum at fixed C6: e_i = -1/2 sum C6 phi; f_i = -sum C6 phi' d / r; dE/dCN_i = -sum phi dC6_ij/dCN_i;
 // strain derivative share s_i[ab] = -1/2 sum C6 phi' d_a d_b / r
-__global__ __launch_bounds__(NTH) void d3_pair_kernel(const double *__restrict__ x, const double *__restrict__ tau, int n, int T,
-                                                      int t_zero, const double *__restrict__ r2r4, const double *__restrict__ r0ab,
+__global__ __launch_bounds__(NTH) void d3_pair_kernel(const D3Sys *__restrict__ sys, const int32_t *__restrict__ sys_of,
+                                                      const double *__restrict__ x, const double *__restrict__ tau,
+                                                      const double *__restrict__ r2r4, const double *__restrict__ r0ab,
                                                       const int32_t *__restrict__ type, int nt, const double *__restrict__ cn,
-                                                      const int32_t *__restrict__ mxc, const double *__restrict__ ref, int t_chunks,
+                                                      const int32_t *__restrict__ mxc, const double *__restrict__ ref,
                                                       double vdw_cut, Func F,
                                                       double *__restrict__ e_atom, double *__restrict__ f, double *__restrict__ dedcn,
                                                       double *__restrict__ s_atom) {
   __shared__ double sh[4];
-  const int i = blockIdx.x;
+  const D3Sys S = sys[sys_of[blockIdx.x]];
+  const int i = (int)(blockIdx.x - S.a0), n = S.n, T = S.Tv, t_zero = S.zv, t_chunks = S.t_chunks;
+  x += 3 * S.a0; tau += 3 * S.tv0; r2r4 += S.a0; type += S.a0; cn += S.a0;
+  e_atom += S.a0; f += 3 * S.a0; dedcn += S.a0; s_atom += 6 * S.a0;
   const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], q_i = r2r4[i];
   double e = 0.0, fx = 0.0, fy = 0.0, fz = 0.0, dc = 0.0, s[6] = {0, 0, 0, 0, 0, 0};
   // work item = (atom j, chunk of the T images): C6_ij is evaluated once per item; t_chunks = 1 for large n, more for small cells whose
@@ -160,12 +177,15 @@ __global__ __launch_bounds__(NTH) void d3_pair_kernel(const double *__restrict__
 }
 
 // CN-gradient part: f_i += sum (dE/dCN_i + dE/dCN_j) cnt'(r) d / r ;  s_i[ab] += sum dE/dCN_i cnt'(r) d_a d_b / r
-__global__ __launch_bounds__(NTH) void d3_cn_force_kernel(const double *__restrict__ x, const double *__restrict__ tau, int n, int T,
-                                                          int t_zero, const double *__restrict__ rcov, double cn_cut,
+__global__ __launch_bounds__(NTH) void d3_cn_force_kernel(const D3Sys *__restrict__ sys, const int32_t *__restrict__ sys_of,
+                                                          const double *__restrict__ x, const double *__restrict__ tau,
+                                                          const double *__restrict__ rcov, double cn_cut,
                                                           const double *__restrict__ dedcn, double *__restrict__ f,
                                                           double *__restrict__ s_atom) {
   __shared__ double sh[4];
-  const int i = blockIdx.x;
+  const D3Sys S = sys[sys_of[blockIdx.x]];
+  const int i = (int)(blockIdx.x - S.a0), n = S.n, T = S.Tc, t_zero = S.zc;
+  x += 3 * S.a0; tau += 3 * S.tc0; rcov += S.a0; dedcn += S.a0; f += 3 * S.a0; s_atom += 6 * S.a0;
   const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2], rci = rcov[i], di = dedcn[i];
   double fx = 0.0, fy = 0.0, fz = 0.0, s[6] = {0, 0, 0, 0, 0, 0};
   const int64_t total = (int64_t)n * T;
@@ -232,8 +252,10 @@ struct snet_d3 {
   // results
   double energy = 0.0, stress[9] = {0};
   std::vector<double> forces, cn;
-  Dev<double> d_x, d_tv, d_tc, d_rcov, d_r2r4, d_r0, d_ref, d_cn, d_e, d_f, d_dedcn, d_s;
-  Dev<int32_t> d_type, d_mxc;
+  // device buffers: the packed inputs (fp64 tables, int32 tables, per-system records) and the work array [e | s | f | cn | dE/dCN]
+  Dev<double> d_in, d_work;
+  Dev<int32_t> d_int;
+  Dev<D3Sys> d_sys;
 };
 
 extern "C" {
@@ -298,6 +320,7 @@ int snet_d3_set_cell(snet_d3 *d, const double *cell9, const int32_t *pbc3) {
   return 0;
 }
 
+// appends the lattice translations within reach of r2_cut to `tau`; t_zero: the index of (0, 0, 0) among those appended
 static void translations(const double a[9], const int pbc[3], double r2_cut, std::vector<double> &tau, int &t_zero) {
   // |n_k| <= int(r_cut / height_k) + 1 along periodic axes (set_lattice_repetition_criteria, :979-1001)
   const double rc = std::sqrt(r2_cut);
@@ -308,95 +331,152 @@ static void translations(const double a[9], const int pbc[3], double r2_cut, std
     const double h = std::fabs((cp[0] * w[0] + cp[1] * w[1] + cp[2] * w[2]) / std::sqrt(cp[0] * cp[0] + cp[1] * cp[1] + cp[2] * cp[2]));
     rep[k] = pbc[k] ? (int)std::fabs(rc / h) + 1 : 0;
   }
-  tau.clear();
+  const size_t base = tau.size();
   t_zero = -1;
   for (int p = -rep[0]; p <= rep[0]; ++p)
     for (int q = -rep[1]; q <= rep[1]; ++q)
       for (int r = -rep[2]; r <= rep[2]; ++r) {
-        if (p == 0 && q == 0 && r == 0) t_zero = (int)(tau.size() / 3);
+        if (p == 0 && q == 0 && r == 0) t_zero = (int)((tau.size() - base) / 3);
         for (int c = 0; c < 3; ++c) tau.push_back(p * a[c] + q * a[3 + c] + r * a[6 + c]);
       }
+}
+
+// B systems [atom_ptr[s], atom_ptr[s+1]) in one set of three launches.  Host work per system as for one: wrap into the cell,
+// build both translation lists, and -- after one readback -- sum the per-atom energy and virial shares in atom order.
+// Outputs: energy[B] (eV), forces[3N] (eV/A), stress[9B] (dE/dstrain / V, eV/A^3), cn[N].  `batch` names the system in errors.
+static int d3_run(snet_d3 *d, int32_t B, const int64_t *atom_ptr, const int32_t *z, const double *pos, const double *cells,
+                  const int32_t *pbc3, double *energy, double *forces, double *stress, double *cn_out, hipStream_t st,
+                  const char *who, bool batch) {
+  auto sys_msg = [&](int s, const std::string &m) {
+    return std::string(who) + ": " + (batch ? "system " + std::to_string(s) + ": " : std::string()) + m;
+  };
+  SNET_REQUIRE(d->have_tables && d->have_func, std::string(who) + ": tables and settings must be set first");
+  SNET_REQUIRE(B >= 1 && atom_ptr[0] == 0, std::string(who) + ": need n_sys >= 1 and atom_ptr[0] == 0");
+  for (int s = 0; s < B; ++s) SNET_REQUIRE(atom_ptr[s + 1] > atom_ptr[s], sys_msg(s, "no atoms (atom_ptr must increase)"));
+  SNET_REQUIRE(atom_ptr[B] <= (int64_t)INT32_MAX, std::string(who) + ": more than 2^31 - 1 atoms in total");
+  const int N = (int)atom_ptr[B];
+  for (int s = 0; s < B; ++s)
+    for (int64_t i = atom_ptr[s]; i < atom_ptr[s + 1]; ++i)
+      SNET_REQUIRE(z[i] >= 1 && z[i] <= 94, sys_msg(s, "Z = " + std::to_string(z[i]) + ": D3 parameters exist for Z = 1 .. 94"));
+  std::vector<double> x(3 * (size_t)N), tv, tc, vol(B);
+  std::vector<D3Sys> sys(B);
+  std::vector<int32_t> sys_of(N);
+  for (int s = 0; s < B; ++s) {
+    const int64_t a0 = atom_ptr[s];
+    const int n = (int)(atom_ptr[s + 1] - a0);
+    double a[9];
+    for (int k = 0; k < 9; ++k) a[k] = cells[9 * (size_t)s + k] / AU_TO_ANG;
+    const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+    SNET_REQUIRE(std::fabs(det) > 1e-12, sys_msg(s, "singular cell (give molecules a box: the reference's calculator does, calculator.py:533-548)"));
+    double inv[9] = {(a[4] * a[8] - a[5] * a[7]) / det, (a[2] * a[7] - a[1] * a[8]) / det, (a[1] * a[5] - a[2] * a[4]) / det,
+                     (a[5] * a[6] - a[3] * a[8]) / det, (a[0] * a[8] - a[2] * a[6]) / det, (a[2] * a[3] - a[0] * a[5]) / det,
+                     (a[3] * a[7] - a[4] * a[6]) / det, (a[1] * a[6] - a[0] * a[7]) / det, (a[0] * a[4] - a[1] * a[3]) / det};
+    // wrap into the cell (load_atom_info, :1170-1219): fractional = x inv(cell), rows of `a` are the lattice vectors
+    for (int i = 0; i < n; ++i) {
+      const double *p = pos + 3 * (a0 + i);
+      double fr[3];
+      for (int c = 0; c < 3; ++c) {
+        fr[c] = 0.0;
+        for (int k = 0; k < 3; ++k) fr[c] += p[k] / AU_TO_ANG * inv[3 * k + c];
+        fr[c] -= std::floor(fr[c]);
+      }
+      for (int c = 0; c < 3; ++c) x[3 * (a0 + i) + c] = fr[0] * a[c] + fr[1] * a[3 + c] + fr[2] * a[6 + c];
+      sys_of[a0 + i] = s;
+    }
+    const int p3[3] = {pbc3[3 * s] != 0, pbc3[3 * s + 1] != 0, pbc3[3 * s + 2] != 0};
+    D3Sys &S = sys[s];
+    S.a0 = a0;
+    S.n = n;
+    S.tv0 = (int64_t)(tv.size() / 3);
+    translations(a, p3, d->vdw_cut, tv, S.zv);
+    S.Tv = (int)((int64_t)(tv.size() / 3) - S.tv0);
+    S.tc0 = (int64_t)(tc.size() / 3);
+    translations(a, p3, d->cn_cut, tc, S.zc);
+    S.Tc = (int)((int64_t)(tc.size() / 3) - S.tc0);
+    // >= 4 work items per thread where the images allow it: from this system's own n and T, as for a single call
+    S.t_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(S.Tv, (4 * NTH + (int64_t)n - 1) / n));
+    vol[s] = std::fabs(det) * AU_TO_ANG * AU_TO_ANG * AU_TO_ANG;
+  }
+  // elements present in the batch -> dense type index and their slice of the reference-C6 grid
+  std::vector<int> type_of(95, -1), elems;
+  std::vector<int32_t> type(N);
+  for (int i = 0; i < N; ++i) {
+    if (type_of[z[i]] < 0) { type_of[z[i]] = (int)elems.size(); elems.push_back(z[i]); }
+    type[i] = type_of[z[i]];
+  }
+  const int nt = (int)elems.size();
+  const size_t nref = (size_t)nt * nt * MAXREF * MAXREF * 3;
+  // packed fp64 inputs: x [3N] | tv | tc | rcov [N] | r2r4 [N] | r0 [nt nt] | ref [nt nt 5 5 3]
+  const size_t o_tv = 3 * (size_t)N, o_tc = o_tv + tv.size(), o_rcov = o_tc + tc.size(), o_r2r4 = o_rcov + N, o_r0 = o_r2r4 + N,
+               o_ref = o_r0 + (size_t)nt * nt, n_in = o_ref + nref;
+  std::vector<double> in(n_in);
+  std::memcpy(in.data(), x.data(), sizeof(double) * x.size());
+  std::memcpy(in.data() + o_tv, tv.data(), sizeof(double) * tv.size());
+  std::memcpy(in.data() + o_tc, tc.data(), sizeof(double) * tc.size());
+  for (int i = 0; i < N; ++i) { in[o_rcov + i] = d->rcov[z[i] - 1]; in[o_r2r4 + i] = d->r2r4[z[i] - 1]; }
+  // packed int32 inputs: type [N] | sys_of [N] | mxc [nt]
+  std::vector<int32_t> ints(2 * (size_t)N + nt);
+  std::memcpy(ints.data(), type.data(), sizeof(int32_t) * N);
+  std::memcpy(ints.data() + N, sys_of.data(), sizeof(int32_t) * N);
+  for (int p = 0; p < nt; ++p) {
+    ints[2 * (size_t)N + p] = d->mxc[elems[p]];
+    for (int q = 0; q < nt; ++q) {
+      std::memcpy(&in[o_ref + ((size_t)p * nt + q) * MAXREF * MAXREF * 3], &d->c6ref[((size_t)elems[p] * 95 + elems[q]) * MAXREF * MAXREF * 3],
+                  sizeof(double) * MAXREF * MAXREF * 3);
+      in[o_r0 + (size_t)p * nt + q] = d->r0ab[(size_t)(elems[p] - 1) * 94 + elems[q] - 1] / AU_TO_ANG;
+    }
+  }
+  // work array: e [N] | s [6N] | f [3N] | cn [N] (read back in one copy) | dE/dCN [N]
+  const size_t o_s = N, o_f = 7 * (size_t)N, o_cn = 10 * (size_t)N, o_dc = 11 * (size_t)N;
+  bool ok = d->d_in.put(in, st) && d->d_int.put(ints, st) && d->d_sys.put(sys, st) && d->d_work.ensure(12 * (size_t)N);
+  SNET_REQUIRE(ok, std::string(who) + ": device allocation / upload failed");
+  const double *X = d->d_in.p, *TV = X + o_tv, *TC = X + o_tc, *RCOV = X + o_rcov, *R2R4 = X + o_r2r4, *R0 = X + o_r0, *REF = X + o_ref;
+  const int32_t *TYPE = d->d_int.p, *SYS_OF = TYPE + N, *MXC = TYPE + 2 * (size_t)N;
+  double *W = d->d_work.p;
+  d3_cn_kernel<<<N, NTH, 0, st>>>(d->d_sys.p, SYS_OF, X, TC, RCOV, d->cn_cut, W + o_cn);
+  d3_pair_kernel<<<N, NTH, 0, st>>>(d->d_sys.p, SYS_OF, X, TV, R2R4, R0, TYPE, nt, W + o_cn, MXC, REF, d->vdw_cut, d->func,
+                                    W, W + o_f, W + o_dc, W + o_s);
+  d3_cn_force_kernel<<<N, NTH, 0, st>>>(d->d_sys.p, SYS_OF, X, TC, RCOV, d->cn_cut, W + o_dc, W + o_f, W + o_s);
+  SNET_CHECK_LAUNCH(who);
+  std::vector<double> out(11 * (size_t)N);
+  ok = hipMemcpyAsync(out.data(), W, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  SNET_REQUIRE(ok, std::string(who) + ": readback failed");
+  const double *e = out.data(), *sa = e + o_s, *f = e + o_f, *cn = e + o_cn;
+  for (int s = 0; s < B; ++s) {
+    double et = 0.0, sv[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t i = atom_ptr[s]; i < atom_ptr[s + 1]; ++i) {   // fixed order: reproducible totals
+      et += e[i];
+      for (int q = 0; q < 6; ++q) sv[q] += sa[6 * (size_t)i + q];
+    }
+    energy[s] = et * AU_TO_EV;
+    const double k = AU_TO_EV / vol[s];
+    const double full[9] = {sv[0], sv[3], sv[4], sv[3], sv[1], sv[5], sv[4], sv[5], sv[2]};
+    for (int q = 0; q < 9; ++q) stress[9 * (size_t)s + q] = full[q] * k;
+  }
+  for (size_t q = 0; q < 3 * (size_t)N; ++q) forces[q] = f[q] * (AU_TO_EV / AU_TO_ANG);
+  std::memcpy(cn_out, cn, sizeof(double) * N);
+  return 0;
 }
 
 int snet_d3_compute(snet_d3 *d, void *stream) {
   SNET_REQUIRE(d != nullptr, "snet_d3_compute: null handle");
   SNET_REQUIRE(d->have_tables && d->have_func && d->have_cell && !d->z.empty(),
                "snet_d3_compute: tables, settings, atoms and cell must be set first");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int n = (int)d->z.size();
-  double a[9];
-  for (int k = 0; k < 9; ++k) a[k] = d->cell[k] / AU_TO_ANG;
-  const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
-  SNET_REQUIRE(std::fabs(det) > 1e-12, "snet_d3_compute: singular cell (give molecules a box: the reference's calculator does, calculator.py:533-548)");
-  double inv[9] = {(a[4] * a[8] - a[5] * a[7]) / det, (a[2] * a[7] - a[1] * a[8]) / det, (a[1] * a[5] - a[2] * a[4]) / det,
-                   (a[5] * a[6] - a[3] * a[8]) / det, (a[0] * a[8] - a[2] * a[6]) / det, (a[2] * a[3] - a[0] * a[5]) / det,
-                   (a[3] * a[7] - a[4] * a[6]) / det, (a[1] * a[6] - a[0] * a[7]) / det, (a[0] * a[4] - a[1] * a[3]) / det};
-  // wrap into the cell (load_atom_info, :1170-1219): fractional = x inv(cell), rows of `a` are the lattice vectors
-  std::vector<double> x(3 * (size_t)n);
-  for (int i = 0; i < n; ++i) {
-    double fr[3];
-    for (int c = 0; c < 3; ++c) {
-      fr[c] = 0.0;
-      for (int k = 0; k < 3; ++k) fr[c] += d->pos[3 * i + k] / AU_TO_ANG * inv[3 * k + c];
-      fr[c] -= std::floor(fr[c]);
-    }
-    for (int c = 0; c < 3; ++c) x[3 * i + c] = fr[0] * a[c] + fr[1] * a[3 + c] + fr[2] * a[6 + c];
-  }
-  std::vector<double> tv, tc;
-  int zv = -1, zc = -1;
-  translations(a, d->pbc, d->vdw_cut, tv, zv);
-  translations(a, d->pbc, d->cn_cut, tc, zc);
-  const int Tv = (int)(tv.size() / 3), Tc = (int)(tc.size() / 3);
-  // elements present -> dense type index and their slice of the reference-C6 grid
-  std::vector<int> type_of(95, -1), elems;
-  std::vector<int32_t> type(n);
-  for (int i = 0; i < n; ++i) {
-    if (type_of[d->z[i]] < 0) { type_of[d->z[i]] = (int)elems.size(); elems.push_back(d->z[i]); }
-    type[i] = type_of[d->z[i]];
-  }
-  const int nt = (int)elems.size();
-  std::vector<double> ref((size_t)nt * nt * MAXREF * MAXREF * 3), r0((size_t)nt * nt), rcov(n), r2r4(n);
-  std::vector<int32_t> mxc(nt);
-  for (int p = 0; p < nt; ++p) {
-    mxc[p] = d->mxc[elems[p]];
-    for (int q = 0; q < nt; ++q) {
-      std::memcpy(&ref[((size_t)p * nt + q) * MAXREF * MAXREF * 3], &d->c6ref[((size_t)elems[p] * 95 + elems[q]) * MAXREF * MAXREF * 3],
-                  sizeof(double) * MAXREF * MAXREF * 3);
-      r0[(size_t)p * nt + q] = d->r0ab[(size_t)(elems[p] - 1) * 94 + elems[q] - 1] / AU_TO_ANG;
-    }
-  }
-  for (int i = 0; i < n; ++i) { rcov[i] = d->rcov[d->z[i] - 1]; r2r4[i] = d->r2r4[d->z[i] - 1]; }
-  bool ok = d->d_x.put(x, st) && d->d_tv.put(tv, st) && d->d_tc.put(tc, st) && d->d_rcov.put(rcov, st) && d->d_r2r4.put(r2r4, st) &&
-            d->d_r0.put(r0, st) && d->d_ref.put(ref, st) && d->d_type.put(type, st) && d->d_mxc.put(mxc, st) &&
-            d->d_cn.ensure(n) && d->d_e.ensure(n) &&
-            d->d_f.ensure(3 * (size_t)n) && d->d_dedcn.ensure(n) && d->d_s.ensure(6 * (size_t)n);
-  SNET_REQUIRE(ok, "snet_d3_compute: device allocation / upload failed");
-  d3_cn_kernel<<<n, NTH, 0, st>>>(d->d_x.p, d->d_tc.p, n, Tc, zc, d->d_rcov.p, d->cn_cut, d->d_cn.p);
-  const int t_chunks = std::max(1, std::min(Tv, (4 * NTH + n - 1) / n));   // >= 4 work items per thread where the images allow it
-  d3_pair_kernel<<<n, NTH, 0, st>>>(d->d_x.p, d->d_tv.p, n, Tv, zv, d->d_r2r4.p, d->d_r0.p, d->d_type.p, nt, d->d_cn.p, d->d_mxc.p,
-                                    d->d_ref.p, t_chunks, d->vdw_cut, d->func, d->d_e.p, d->d_f.p, d->d_dedcn.p, d->d_s.p);
-  d3_cn_force_kernel<<<n, NTH, 0, st>>>(d->d_x.p, d->d_tc.p, n, Tc, zc, d->d_rcov.p, d->cn_cut, d->d_dedcn.p, d->d_f.p, d->d_s.p);
-  SNET_CHECK_LAUNCH("snet_d3_compute");
-  std::vector<double> e(n), s(6 * (size_t)n);
-  d->forces.resize(3 * (size_t)n);
-  d->cn.resize(n);
-  ok = hipMemcpyAsync(e.data(), d->d_e.p, sizeof(double) * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(s.data(), d->d_s.p, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(d->forces.data(), d->d_f.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipMemcpyAsync(d->cn.data(), d->d_cn.p, sizeof(double) * n, hipMemcpyDeviceToHost, st) == hipSuccess &&
-       hipStreamSynchronize(st) == hipSuccess;
-  SNET_REQUIRE(ok, "snet_d3_compute: readback failed");
-  double et = 0.0, sv[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < n; ++i) {   // fixed order: reproducible totals
-    et += e[i];
-    for (int q = 0; q < 6; ++q) sv[q] += s[6 * (size_t)i + q];
-  }
-  d->energy = et * AU_TO_EV;
-  for (auto &v : d->forces) v *= AU_TO_EV / AU_TO_ANG;
-  const double vol = std::fabs(det) * AU_TO_ANG * AU_TO_ANG * AU_TO_ANG, k = AU_TO_EV / vol;
-  const double full[9] = {sv[0], sv[3], sv[4], sv[3], sv[1], sv[5], sv[4], sv[5], sv[2]};
-  for (int q = 0; q < 9; ++q) d->stress[q] = full[q] * k;
-  return 0;
+  const int64_t atom_ptr[2] = {0, (int64_t)d->z.size()};
+  d->forces.resize(3 * d->z.size());
+  d->cn.resize(d->z.size());
+  return d3_run(d, 1, atom_ptr, d->z.data(), d->pos.data(), d->cell, d->pbc, &d->energy, d->forces.data(), d->stress, d->cn.data(),
+                static_cast<hipStream_t>(stream), "snet_d3_compute", false);
+}
+
+int snet_d3_compute_batch(snet_d3 *d, int32_t n_sys, const int64_t *atom_ptr, const int32_t *atomic_numbers, const double *positions,
+                          const double *cells, const int32_t *pbc, double *energy, double *forces, double *stress, double *cn,
+                          void *stream) {
+  SNET_REQUIRE(d && atom_ptr && atomic_numbers && positions && cells && pbc && energy && forces && stress && cn,
+               "snet_d3_compute_batch: null argument");
+  return d3_run(d, n_sys, atom_ptr, atomic_numbers, positions, cells, pbc, energy, forces, stress, cn, static_cast<hipStream_t>(stream),
+                "snet_d3_compute_batch", true);
 }
 
 double snet_d3_energy(const snet_d3 *d) { return d ? d->energy : 0.0; }

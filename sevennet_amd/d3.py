@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict
+from typing import Any, Dict, List, NamedTuple
 
 import numpy as np
 
@@ -22,6 +22,64 @@ _DAMPING = {'damp_zero': 0, 'damp_bj': 1}
 
 def _dp(a):
     return C.c_void_p(a.ctypes.data)
+
+
+def molecule_box(positions, cell, pbc, rthr: float, cnthr: float):
+    """(cell [3,3], pbc [3]) that D3 evaluates: a cell that sums to zero becomes an orthogonal periodic box larger than the
+    longest cutoff, extent + sqrt(max(rthr, cnthr)) bohr + 1 A (sevenn/calculator.py:533-548); any other cell is kept"""
+    positions = np.asarray(positions, np.float64).reshape(-1, 3)
+    cell = np.array(cell, np.float64).reshape(3, 3)
+    pbc = np.asarray(pbc, bool).reshape(3)
+    if cell.sum() == 0:
+        max_cutoff = np.sqrt(max(rthr, cnthr)) * AU_TO_ANG
+        cell = np.eye(3) * (positions.max(0) - positions.min(0) + max_cutoff + 1.0)
+        pbc = np.array([True, True, True])
+    return cell, pbc
+
+
+class D3Batch(NamedTuple):
+    """flat host inputs of snet_d3_compute_batch: system s owns atoms [atom_ptr[s], atom_ptr[s+1])"""
+    atom_ptr: np.ndarray    # int64 [B+1]
+    numbers: np.ndarray     # int32 [N]
+    positions: np.ndarray   # float64 [N,3], A
+    cells: np.ndarray       # float64 [B,3,3], A, after the molecule box
+    pbcs: np.ndarray        # int32 [B,3], after the molecule box
+
+
+def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float, n_atoms=None) -> D3Batch:
+    """Host-side preparation of a D3 batch, with no device work.  numbers / positions: per-system sequences, or flat
+    arrays together with n_atoms[B] (the shape rules of SevenNetCalculator.compute_many); cells[B,3,3] (rows = lattice
+    vectors), pbcs[B,3] or one [3].  Applies `molecule_box` per system.  Raises ValueError on an empty batch or system,
+    mismatched lengths, Z outside 1..94 and a cell that is singular after the box rule."""
+    from .batch import _as_host, _normalize
+    numbers, positions, n_at, cells, pbcs = _normalize(numbers, positions, cells, pbcs, n_atoms)
+    numbers = _as_host(numbers, np.int64).reshape(-1)
+    positions = np.ascontiguousarray(_as_host(positions, np.float64).reshape(-1, 3))
+    atom_ptr = np.concatenate([[0], np.cumsum(n_at)]).astype(np.int64)
+    if atom_ptr[-1] > 2 ** 31 - 1:
+        raise ValueError(f'{int(atom_ptr[-1])} atoms: at most 2^31 - 1 in one D3 batch')
+    bad = (numbers < 1) | (numbers > 94)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {int(np.searchsorted(atom_ptr, i, side="right")) - 1}: Z = {int(numbers[i])} '
+                         'has no D3 parameters (Z = 1 .. 94)')
+    B = len(n_at)
+    cells_out, pbcs_out = np.empty((B, 3, 3)), np.empty((B, 3), np.int32)
+    for b in range(B):
+        cell, pbc = molecule_box(positions[atom_ptr[b]:atom_ptr[b + 1]], cells[b], pbcs[b], rthr, cnthr)
+        if not abs(np.linalg.det(cell / AU_TO_ANG)) > 1e-12:   # the bound of snet_d3_compute (bohr^3)
+            raise ValueError(f'system {b}: singular cell {cell.tolist()} (pbc {pbc.tolist()})')
+        cells_out[b], pbcs_out[b] = cell, pbc
+    return D3Batch(atom_ptr, np.ascontiguousarray(numbers, np.int32), positions, cells_out, pbcs_out)
+
+
+def _atoms_args(atoms_list):
+    """(numbers_list, positions_list, cells[B,3,3], pbcs[B,3]) of ASE-like objects (get_atomic_numbers / get_positions /
+    get_cell / get_pbc)"""
+    atoms_list = list(atoms_list)
+    return ([a.get_atomic_numbers() for a in atoms_list], [a.get_positions() for a in atoms_list],
+            np.array([np.array(a.get_cell(), np.float64).reshape(3, 3) for a in atoms_list]).reshape(-1, 3, 3),
+            np.array([np.asarray(a.get_pbc(), bool).reshape(3) for a in atoms_list]).reshape(-1, 3))
 
 
 class D3Engine:
@@ -53,13 +111,7 @@ class D3Engine:
         import torch
         numbers = np.ascontiguousarray(numbers, np.int32)
         positions = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
-        cell = np.array(cell, np.float64).reshape(3, 3)
-        pbc = np.asarray(pbc, bool).reshape(3)
-        if cell.sum() == 0:
-            # sevenn/calculator.py:533-548: molecules get an orthogonal periodic box larger than the longest cutoff
-            max_cutoff = np.sqrt(max(self.rthr, self.cnthr)) * AU_TO_ANG
-            cell = np.eye(3) * (positions.max(0) - positions.min(0) + max_cutoff + 1.0)
-            pbc = np.array([True, True, True])
+        cell, pbc = molecule_box(positions, cell, pbc, self.rthr, self.cnthr)
         n = len(numbers)
         _lib.check(self.lib.snet_d3_set_atoms(self.handle, n, _dp(numbers), _dp(positions)), 'snet_d3_set_atoms')
         cell_c = np.ascontiguousarray(cell)
@@ -70,6 +122,20 @@ class D3Engine:
         s = np.ctypeslib.as_array(self.lib.snet_d3_stress(self.handle), shape=(3, 3)).copy()
         cn = np.ctypeslib.as_array(self.lib.snet_d3_coordination_numbers(self.handle), shape=(n,)).copy()
         return dict(energy=float(self.lib.snet_d3_energy(self.handle)), forces=f, stress=s, cn=cn)
+
+    def compute_many(self, numbers_list, positions_list, cells, pbcs, n_atoms=None) -> List[Dict[str, Any]]:
+        """`compute` for B systems in one snet_d3_compute_batch call (three kernel launches, one readback): one dict per
+        system, in the given order, equal bit for bit to `compute` on that system.  Inputs as `prepare_d3_batch`."""
+        import torch
+        bt = prepare_d3_batch(numbers_list, positions_list, cells, pbcs, self.rthr, self.cnthr, n_atoms=n_atoms)
+        B, N = len(bt.atom_ptr) - 1, len(bt.numbers)
+        energy, forces, stress, cn = np.empty(B), np.empty((N, 3)), np.empty((B, 3, 3)), np.empty(N)
+        _lib.check(self.lib.snet_d3_compute_batch(self.handle, B, _dp(bt.atom_ptr), _dp(bt.numbers), _dp(bt.positions),
+                                                  _dp(bt.cells), _dp(bt.pbcs), _dp(energy), _dp(forces), _dp(stress), _dp(cn),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'snet_d3_compute_batch')
+        ap = bt.atom_ptr
+        return [dict(energy=float(energy[b]), forces=forces[ap[b]:ap[b + 1]], stress=stress[b], cn=cn[ap[b]:ap[b + 1]])
+                for b in range(B)]
 
     def __del__(self):
         try:
@@ -109,11 +175,22 @@ class D3Calculator(Calculator):
         self.rthr, self.cnthr = self.engine.rthr, self.engine.cnthr
         self.damp_name, self.func_name = self.engine.damp_name, self.engine.func_name
 
-    def compute(self, numbers, positions, cell, pbc) -> Dict[str, Any]:
-        r = self.engine.compute(numbers, positions, cell, pbc)
+    @staticmethod
+    def _results(r) -> Dict[str, Any]:
         s = r['stress']
         return {'free_energy': r['energy'], 'energy': r['energy'], 'forces': r['forces'],
                 'stress': np.array([s[0, 0], s[1, 1], s[2, 2], s[1, 2], s[0, 2], s[0, 1]])}
+
+    def compute(self, numbers, positions, cell, pbc) -> Dict[str, Any]:
+        return self._results(self.engine.compute(numbers, positions, cell, pbc))
+
+    def compute_many(self, numbers_list, positions_list, cells, pbcs, n_atoms=None) -> List[Dict[str, Any]]:
+        """`compute` for B systems in one D3Engine.compute_many call: one dict per system, in the given order"""
+        return [self._results(r) for r in self.engine.compute_many(numbers_list, positions_list, cells, pbcs, n_atoms=n_atoms)]
+
+    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
+        """`compute_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc)"""
+        return self.compute_many(*_atoms_args(atoms_list))
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         Calculator.calculate(self, atoms, properties, system_changes)
@@ -160,9 +237,24 @@ class SevenNetD3Calculator(_SumBase):
         else:
             self.calcs = list(pair)
 
-    def compute(self, numbers, positions, cell, pbc) -> Dict[str, Any]:
-        a, b = (c.compute(numbers, positions, cell, pbc) for c in self.calcs)
+    @staticmethod
+    def _sum(a, b) -> Dict[str, Any]:
         out = dict(a)
         for k in ('free_energy', 'energy', 'forces', 'stress'):
             out[k] = a[k] + b[k]
         return out
+
+    def compute(self, numbers, positions, cell, pbc) -> Dict[str, Any]:
+        a, b = (c.compute(numbers, positions, cell, pbc) for c in self.calcs)
+        return self._sum(a, b)
+
+    def compute_many(self, numbers_list, positions_list, cells, pbcs) -> List[Dict[str, Any]]:
+        """`compute` for B structures: one SevenNetCalculator.compute_many and one D3Calculator.compute_many call, summed
+        per system as `compute` sums them (cells[B,3,3], pbcs[B,3] or one [3])"""
+        numbers_list, positions_list = list(numbers_list), list(positions_list)
+        a, b = (c.compute_many(numbers_list, positions_list, cells, pbcs) for c in self.calcs)
+        return [self._sum(x, y) for x, y in zip(a, b)]
+
+    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
+        """`compute_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc)"""
+        return self.compute_many(*_atoms_args(atoms_list))
