@@ -417,6 +417,26 @@ int snet_batch_nl_fill(const double *pos, const int32_t *atom_ptr, int32_t n_sys
                        int64_t n_atoms, double cutoff, const int32_t *row_ptr, int32_t *src, int32_t *center,
                        float *edge_vec, int32_t *shifts, void *stream);
 
+/* ---- batched FIRE relaxation step (fixed cell, unit masses) -------------------------------------
+ * One step of FIRE (Bitzek et al., Phys. Rev. Lett. 97, 170201 (2006), as ASE's optimizer states it) for n_sys systems in ONE
+ * launch: the atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32, as Graph.seg_ptr) of pos / vel (fp64
+ * [n_atoms,3], updated in place) and of forces (fp32 [n_atoms,3], as the engine returns them; forces_extra, fp64 [n_atoms,3] or
+ * NULL, is added to them).  Per-system state on the device: dt, alpha (fp64 [n_sys]), n_pos, active, n_steps (int32 [n_sys]).
+ * For every system with active == 1, in fp64 with F the summed forces:
+ *   fm = max_i |F_i|; fmax_sys[s] = fm; if fm < fmax: active = 0 and nothing else changes (converged at these positions)
+ *   P = sum F.v;  P > 0: v = (1 - alpha) v + alpha F / |F| |v|; if n_pos > n_min: dt = min(dt f_inc, dt_max), alpha *= f_alpha;
+ *                        n_pos += 1
+ *                 else:  v = 0, alpha = alpha_start, dt *= f_dec, n_pos = 0
+ *   v += dt F;  dr = dt v, scaled to length max_step if longer (norm over the whole system);  pos += dr;  n_steps += 1
+ * Systems with active == 0 are not touched.  *n_active (device int32) receives the number of systems still active.
+ * dt_start is the value the caller initialised dt[] with (range-checked with the others, not read by the step).
+ * One workgroup per system, fp64 sums in a fixed order: two runs give identical bits.  Calls on one device must follow
+ * each other in stream order.  */
+int snet_fire_step(double *pos, double *vel, const float *forces, const double *forces_extra, int64_t n_atoms,
+                   const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos, int32_t *active,
+                   int32_t *n_steps, double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max,
+                   int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step, void *stream);
+
 /* ---- whole-model sequencer ------------------------------------------------------------------
  * replaces, for a native (C++) host, `model.forward(input_dict)` + `torch::autograd::grad(...)` of
  * the LAMMPS pair styles (sevenn/pair_e3gnn/pair_e3gnn.cpp:200-207, pair_e3gnn_parallel.cpp:424-503)

@@ -263,6 +263,27 @@ def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species:
         return concat_graphs(pieces, num_species if species_rows else 0, share_pairs)
 
 
+def batch_results(g: Graph, out: dict, cells, with_atomic_virial: bool = False) -> List[dict]:
+    """one results dict per system of a batch graph `g` from the engine's output `out` for it: the keys, units, Voigt order
+    and stress sign of SevenNetCalculator.compute (cells[B,3,3] gives the volumes)"""
+    sp = g.seg_ptr_host
+    e_sys = out['energy_per_system'].cpu().numpy()
+    stress = virial_to_stress(out['virial_per_system'].cpu().numpy(), np.asarray(cells, np.float64).reshape(-1, 3, 3))
+    energies = out['atomic_energy'].cpu().numpy().astype(np.float64)
+    forces = out['forces'].cpu().numpy().astype(np.float64)
+    n_edges = np.diff(g.row_ptr[torch.as_tensor(sp).to(g.row_ptr.device)].cpu().numpy())
+    atomic_virial = out['atomic_virial'].cpu().numpy() if with_atomic_virial else None
+    results = []
+    for b in range(len(sp) - 1):
+        a0, a1 = int(sp[b]), int(sp[b + 1])
+        res = {'free_energy': float(e_sys[b]), 'energy': float(e_sys[b]), 'energies': energies[a0:a1],
+               'forces': forces[a0:a1], 'stress': stress[b], 'num_edges': int(n_edges[b])}
+        if atomic_virial is not None:
+            res['stresses'] = atomic_virial[a0:a1]
+        results.append(res)
+    return results
+
+
 def virial_to_stress(virial: np.ndarray, cells: np.ndarray) -> np.ndarray:
     """[B,6] ASE Voigt stress (xx,yy,zz,yz,xz,xy, eV/A^3) from the engine's virial[B,6] (model order xx,yy,zz,xy,yz,zx) and
     cells[B,3,3]: -(virial / volume)[[0,1,2,4,5,3]] as SevenNetCalculator.compute (sevenn/calculator.py:198-203); NaN for a

@@ -235,6 +235,7 @@ class SevenNetCalculator(Calculator):
             warnings.warn(f'modal={modal} is ignored as model has no modal_map')
         self.model = HipForceEngine(cfg, sd, device=str(self.device), modal=self.modal)
         self._z2type = np.full(120, -1, np.int64)  # sequential.py:80-83
+        self.relax_info: Optional[Dict[str, int]] = None   # counters of the last relax_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -275,12 +276,8 @@ class SevenNetCalculator(Calculator):
             res['stresses'] = out['atomic_virial'].cpu().numpy()
         return res
 
-    def compute_many(self, numbers_list, positions_list, cells, pbcs) -> List[Dict[str, Any]]:
-        """`compute` for B structures in ONE engine call (sevennet_amd.batch): one results dict per system, in the given
-        order, with the keys, units, Voigt order and stress sign of `compute`.  cells[B,3,3], pbcs[B,3] (or one [3])."""
-        from .batch import build_batch_graph, virial_to_stress
-        if len(numbers_list) != len(positions_list):
-            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+    def _types_list(self, numbers_list) -> List[np.ndarray]:
+        """species indices of each system's atomic numbers; ValueError on one the model does not know"""
         types_list = []
         for numbers in numbers_list:
             numbers = np.asarray(numbers, np.int64).reshape(-1)
@@ -289,25 +286,44 @@ class SevenNetCalculator(Calculator):
                 bad = sorted(set(numbers[(types < 0) | (numbers < 0) | (numbers >= len(self._z2type))].tolist()))
                 raise ValueError(f'Model do not know atomic number: {bad[0]}, (knows: {list(self.type_map.keys())})')
             types_list.append(types)
+        return types_list
+
+    def compute_many(self, numbers_list, positions_list, cells, pbcs) -> List[Dict[str, Any]]:
+        """`compute` for B structures in ONE engine call (sevennet_amd.batch): one results dict per system, in the given
+        order, with the keys, units, Voigt order and stress sign of `compute`.  cells[B,3,3], pbcs[B,3] (or one [3])."""
+        from .batch import batch_results, build_batch_graph
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        types_list = self._types_list(numbers_list)
         ns = self.model.spec.num_species
         g = build_batch_graph(types_list, list(positions_list), cells, pbcs, self.cutoff, ns, device=str(self.device),
                               species_rows=self.model.needs_species_rows)
         out = self.model.compute(g, want_atomic_virial=self.compute_atomic_virial)
-        sp = g.seg_ptr_host
-        e_sys = out['energy_per_system'].cpu().numpy()
-        stress = virial_to_stress(out['virial_per_system'].cpu().numpy(), np.asarray(cells, np.float64).reshape(-1, 3, 3))
-        energies = out['atomic_energy'].cpu().numpy().astype(np.float64)
-        forces = out['forces'].cpu().numpy().astype(np.float64)
-        n_edges = np.diff(g.row_ptr[torch.as_tensor(sp).to(g.row_ptr.device)].cpu().numpy())
-        atomic_virial = out['atomic_virial'].cpu().numpy() if self.compute_atomic_virial else None
-        results = []
-        for b in range(len(sp) - 1):
-            a0, a1 = int(sp[b]), int(sp[b + 1])
-            res: Dict[str, Any] = {'free_energy': float(e_sys[b]), 'energy': float(e_sys[b]), 'energies': energies[a0:a1],
-                                   'forces': forces[a0:a1], 'stress': stress[b], 'num_edges': int(n_edges[b])}
-            if atomic_virial is not None:
-                res['stresses'] = atomic_virial[a0:a1]
-            results.append(res)
+        return batch_results(g, out, cells, self.compute_atomic_virial)
+
+    def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """Fixed-cell FIRE relaxation of B structures at once (sevennet_amd.relax.relax_batch): positions, velocities and the
+        optimizer state stay on the GPU from the first step to the last, converged systems stop moving at once and leave the
+        batch when enough have finished.  One dict per system, in the given order: the keys of `compute` (evaluated at the
+        returned positions) plus `positions` [n,3] fp64, `converged` (largest atomic force below fmax, eV/A) and `n_steps`.
+        A system that is not converged after `steps` steps is returned with converged = False.  kw: repack_below and the
+        FIRE parameters (relax.FIRE_DEFAULTS).  The call's counters are kept as `self.relax_info`."""
+        from .relax import relax_batch
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        results, self.relax_info = relax_batch(self.model, self._types_list(numbers_list), list(positions_list), cells, pbcs,
+                                               cutoff=self.cutoff, fmax=fmax, steps=steps,
+                                               want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """`relax_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc / set_positions): the
+        relaxed positions are written back with `set_positions`"""
+        from .d3 import _atoms_args
+        atoms_list = list(atoms_list)
+        results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
         return results
 
     def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:

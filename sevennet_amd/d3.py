@@ -73,6 +73,11 @@ def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float,
     return D3Batch(atom_ptr, np.ascontiguousarray(numbers, np.int32), positions, cells_out, pbcs_out)
 
 
+def _as_host_f64(x) -> np.ndarray:
+    from .batch import _as_host
+    return _as_host(x, np.float64)
+
+
 def _atoms_args(atoms_list):
     """(numbers_list, positions_list, cells[B,3,3], pbcs[B,3]) of ASE-like objects (get_atomic_numbers / get_positions /
     get_cell / get_pbc)"""
@@ -236,6 +241,7 @@ class SevenNetD3Calculator(_SumBase):
             super().__init__(list(pair))
         else:
             self.calcs = list(pair)
+        self.relax_info = None   # counters of the last relax_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -258,3 +264,44 @@ class SevenNetD3Calculator(_SumBase):
     def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
         """`compute_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc)"""
         return self.compute_many(*_atoms_args(atoms_list))
+
+    def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.relax_many` on the sum of the model's and the D3 forces (sevennet_amd.relax): one dict per
+        system with the keys of `compute` plus `positions`, `converged` and `n_steps`; the results are `compute_many` at the
+        returned positions, the counters are kept as `self.relax_info`.  `D3Engine.compute_many` prepares its batch on the
+        host, so this path copies the positions down and the D3 forces up once per step (the model's forces and the
+        optimizer state stay on the device)."""
+        import torch
+        from .relax import attach_relaxed, check_fire_params, fire_loop, validate_relax_inputs
+        snet, d3 = self.calcs
+        numbers_list, positions_list = list(numbers_list), list(positions_list)
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        repack_below = kw.pop('repack_below', 0.5)
+        params = check_fire_params(fmax, steps, repack_below, kw)
+        types, positions, n_at, cells_n, pbcs_n = validate_relax_inputs(snet._types_list(numbers_list), positions_list, cells, pbcs,
+                                                                        snet.cutoff, snet.model.spec.num_species)
+        numbers = np.concatenate([np.asarray(z, np.int64).reshape(-1) for z in numbers_list])
+        prepare_d3_batch(numbers, _as_host_f64(positions), cells_n, pbcs_n, d3.rthr, d3.cnthr, n_atoms=n_at)   # Z range, cells
+        a_ptr = np.concatenate([[0], np.cumsum(n_at)])
+
+        def d3_forces(pos_dev, seg_ptr_host, ids):
+            z = np.concatenate([numbers[a_ptr[b]:a_ptr[b + 1]] for b in ids])
+            res = d3.engine.compute_many(z, pos_dev.cpu().numpy(), cells_n[ids], pbcs_n[ids], n_atoms=n_at[ids])
+            return torch.as_tensor(np.concatenate([r['forces'] for r in res])).to(pos_dev.device)
+
+        final, n_steps, converged, info = fire_loop(snet.model, types, positions, n_at, cells_n, pbcs_n, cutoff=snet.cutoff, fmax=fmax,
+                                                    steps=steps, repack_below=repack_below, params=params, extra=d3_forces)
+        pos_h = final.cpu().numpy()
+        results = self.compute_many(numbers_list, [pos_h[a_ptr[b]:a_ptr[b + 1]] for b in range(len(n_at))], cells, pbcs)
+        info['n_force_calls'] += 1
+        self.relax_info = info
+        return attach_relaxed(results, final, a_ptr, n_steps, converged)
+
+    def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """`relax_many` over ASE-like objects; the relaxed positions are written back with `set_positions`"""
+        atoms_list = list(atoms_list)
+        results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
+        return results

@@ -1,0 +1,230 @@
+"""Batched fixed-cell geometry relaxation with FIRE, positions on the device from the first step to the last.
+
+`relax_batch` relaxes B structures at once: per step one batched neighbor build (sevennet_amd.batch), one engine call and one
+`snet_fire_step` launch (csrc/snet_relax.hip: one workgroup per system, fp64, fixed summation order).  Positions, velocities
+and the per-system optimizer state (dt, alpha, n_pos, active, n_steps) are device tensors; the only thing the optimizer reads
+back per step is the number of systems still active.  A system whose largest atomic force is below `fmax` stops moving in the
+same launch that finds it so, and when enough systems have finished the batch is rebuilt from the active ones only (the
+"repack"), so the engine stops paying for structures that converged long ago.
+
+FIRE: Bitzek, Koskinen, Gaehler, Moseler, Gumbsch, Phys. Rev. Lett. 97, 170201 (2006), as ASE's optimizer states it, with unit
+masses; the step rule is written out in include/snet_hip.h (snet_fire_step) and restated in fp64 numpy in tests/relax_ref.py.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Callable, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .batch import BATCH_MAX_ATOMS, _as_host, _normalize, batch_results, build_batch_graph, classify_systems
+
+FIRE_DEFAULTS = dict(dt_start=0.1, dt_max=1.0, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, max_step=0.2)
+
+
+def check_fire_params(fmax: float, steps: int, repack_below: float, fire: dict) -> dict:
+    """FIRE_DEFAULTS overridden by `fire`, range-checked (ValueError) together with fmax, steps and repack_below"""
+    unknown = sorted(set(fire) - set(FIRE_DEFAULTS))
+    if unknown:
+        raise ValueError(f'unknown FIRE parameter {unknown[0]!r} (known: {sorted(FIRE_DEFAULTS)})')
+    p = dict(FIRE_DEFAULTS, **fire)
+    if not fmax >= 0:
+        raise ValueError(f'fmax = {fmax}: the force threshold cannot be negative')
+    if int(steps) != steps or steps < 0:
+        raise ValueError(f'steps = {steps}: a non-negative integer is required')
+    if not 0 <= repack_below <= 1:
+        raise ValueError(f'repack_below = {repack_below}: a fraction in [0, 1] is required (0 switches repacking off)')
+    if int(p['n_min']) != p['n_min'] or p['n_min'] < 0:
+        raise ValueError(f'n_min = {p["n_min"]}: a non-negative integer is required')
+    ok = {'dt_start': p['dt_start'] > 0, 'dt_max': p['dt_max'] >= p['dt_start'], 'f_inc': p['f_inc'] >= 1,
+          'f_dec': 0 < p['f_dec'] < 1, 'alpha_start': 0 < p['alpha_start'] <= 1, 'f_alpha': 0 < p['f_alpha'] <= 1,
+          'max_step': p['max_step'] > 0}
+    for k, good in ok.items():
+        if not good:   # (a NaN fails every comparison)
+            raise ValueError(f'FIRE parameter {k} = {p[k]} is out of range (dt_max >= dt_start > 0, f_inc >= 1, 0 < f_dec < 1, '
+                             '0 < alpha_start <= 1, 0 < f_alpha <= 1, max_step > 0)')
+    p['n_min'] = int(p['n_min'])
+    return p
+
+
+def validate_relax_inputs(types, positions, cells, pbcs, cutoff: float, num_species: int, n_atoms=None,
+                          max_atoms: int = BATCH_MAX_ATOMS):
+    """Everything `build_batch_graph` would reject, found on the host before the first launch: -> (types int64 [N] on the
+    host, positions [N,3] (host array or the caller's tensor), n_atoms [B], cells [B,3,3], pbcs [B,3]).  ValueError names the
+    system."""
+    types, positions, n_at, cells, pbcs = _normalize(types, positions, cells, pbcs, n_atoms)
+    types = _as_host(types, np.int64).reshape(-1)
+    a_ptr = np.concatenate([[0], np.cumsum(n_at)])
+    bad = (types < 0) | (types >= num_species)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {int(np.searchsorted(a_ptr, i, side="right")) - 1}: unknown species index {int(types[i])} '
+                         f'(the model has {num_species})')
+    if not isinstance(positions, torch.Tensor):   # (device tensors are not read back for this)
+        fin = np.isfinite(positions).all(1)
+        if not fin.all():
+            i = int(np.nonzero(~fin)[0][0])
+            raise ValueError(f'system {int(np.searchsorted(a_ptr, i, side="right")) - 1}: non-finite position')
+    if not cutoff > 0:
+        raise ValueError(f'cutoff = {cutoff}: a positive cutoff is required')
+    classify_systems(n_at, cells, pbcs, cutoff, max_atoms)   # singular cells
+    return types, positions, n_at, cells, pbcs
+
+
+class RepackBook:
+    """Host bookkeeping of a shrinking batch: which of the caller's systems are in the current batch (in their original
+    relative order), and the final positions, step counts and flags of those that have left it."""
+
+    def __init__(self, n_atoms):
+        self.n_atoms = np.asarray(n_atoms, np.int64)
+        self.B = len(self.n_atoms)
+        self.ids = np.arange(self.B)               # current batch slot -> caller's system
+        self.positions: List[Any] = [None] * self.B
+        self.n_steps = np.zeros(self.B, np.int64)
+        self.converged = np.zeros(self.B, bool)
+        self.n_repacks = 0
+
+    def seg_ptr(self) -> np.ndarray:
+        return np.concatenate([[0], np.cumsum(self.n_atoms[self.ids])]).astype(np.int64)
+
+    @staticmethod
+    def wants_repack(n_active: int, n_current: int, repack_below: float) -> bool:
+        """some system has finished since the batch was last built, some are left, and at most repack_below of it is active"""
+        return 0 < n_active < n_current and n_active <= repack_below * n_current
+
+    def store(self, pos, active: np.ndarray, n_steps: np.ndarray, only_finished: bool) -> None:
+        """keep the results of the current batch's systems (`pos`: their flat positions, sliceable): the finished ones, or all"""
+        sp = self.seg_ptr()
+        for k, b in enumerate(self.ids):
+            if only_finished and active[k]:
+                continue
+            self.positions[b] = pos[int(sp[k]):int(sp[k + 1])]
+            self.n_steps[b] = int(n_steps[k])
+            self.converged[b] = not active[k]
+
+    def repack(self, pos, active: np.ndarray, n_steps: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """store the finished systems and drop them: -> (slots kept, atom rows kept), both in the old batch's numbering"""
+        self.store(pos, active, n_steps, only_finished=True)
+        sp = self.seg_ptr()
+        keep = np.nonzero(np.asarray(active) != 0)[0]
+        rows = np.concatenate([np.arange(sp[k], sp[k + 1]) for k in keep]) if len(keep) else np.zeros(0, np.int64)
+        self.ids = self.ids[keep]
+        self.n_repacks += 1
+        return keep, rows
+
+
+def fire_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, seg_ptr: torch.Tensor, dt: torch.Tensor,
+              alpha: torch.Tensor, n_pos: torch.Tensor, active: torch.Tensor, n_steps: torch.Tensor, fmax_sys: torch.Tensor,
+              n_active: torch.Tensor, fmax: float, params: dict, forces_extra: Optional[torch.Tensor] = None) -> None:
+    """one `snet_fire_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C ABI:
+    pos / vel / dt / alpha / fmax_sys fp64, forces fp32, forces_extra fp64, the rest int32)"""
+    N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
+    want = [(pos, torch.float64, (N, 3)), (vel, torch.float64, (N, 3)), (forces, torch.float32, (N, 3)), (seg_ptr, torch.int32, (B + 1,)),
+            (dt, torch.float64, (B,)), (alpha, torch.float64, (B,)), (n_pos, torch.int32, (B,)), (active, torch.int32, (B,)),
+            (n_steps, torch.int32, (B,)), (fmax_sys, torch.float64, (B,)), (n_active, torch.int32, (1,))]
+    if forces_extra is not None:
+        want.append((forces_extra, torch.float64, (N, 3)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != pos.device or not t.is_cuda:
+            raise ValueError(f'fire_step: a contiguous {dtype} tensor of shape {shape} on {pos.device} is required, got '
+                             f'{t.dtype} {tuple(t.shape)} on {t.device}')
+    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    with torch.cuda.device(pos.device):
+        _lib.check(_lib.load().snet_fire_step(
+            P(pos), P(vel), P(forces), P(forces_extra), N, P(seg_ptr), B, P(dt), P(alpha), P(n_pos), P(active), P(n_steps),
+            P(fmax_sys), P(n_active), float(fmax), params['dt_start'], params['dt_max'], params['n_min'], params['f_inc'],
+            params['f_dec'], params['alpha_start'], params['f_alpha'], params['max_step'],
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'snet_fire_step')
+
+
+def fire_loop(engine, types: np.ndarray, positions, n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, *, cutoff: float,
+              fmax: float, steps: int, repack_below: float, params: dict, extra: Optional[Callable] = None):
+    """The relaxation loop on validated inputs (`validate_relax_inputs`, `check_fire_params`): -> (positions fp64 [N,3] on the
+    device in the caller's order, n_steps [B], converged [B], info)"""
+    dev = engine.dev
+    ns = engine.spec.num_species
+    book = RepackBook(n_atoms)
+    B = book.B
+    with torch.cuda.device(dev):
+        pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
+               else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).clone()
+        ty = torch.as_tensor(types.astype(np.int32)).to(dev)
+        vel = torch.zeros_like(pos)
+        dt = torch.full((B,), float(params['dt_start']), dtype=torch.float64, device=dev)
+        alpha = torch.full((B,), float(params['alpha_start']), dtype=torch.float64, device=dev)
+        n_pos = torch.zeros(B, dtype=torch.int32, device=dev)
+        active = torch.ones(B, dtype=torch.int32, device=dev)
+        n_steps = torch.zeros(B, dtype=torch.int32, device=dev)
+        fmax_sys = torch.zeros(B, dtype=torch.float64, device=dev)
+        n_active = torch.zeros(1, dtype=torch.int32, device=dev)
+        info = dict(n_force_calls=0, n_repacks=0, system_steps_evaluated=0, fire_launches=0)
+        for _ in range(int(steps)):
+            ids = book.ids
+            sp_host = book.seg_ptr()
+            g = build_batch_graph(ty, pos, cells[ids], pbcs[ids], cutoff, ns, n_atoms=n_atoms[ids], device=dev,
+                                  species_rows=engine.needs_species_rows)
+            out = engine.compute(g)
+            fx = None
+            if extra is not None:
+                fx = extra(pos, sp_host, ids).to(dev, torch.float64).contiguous()
+            fire_step(pos, vel, out['forces'], g.seg_ptr, dt, alpha, n_pos, active, n_steps, fmax_sys, n_active, fmax, params, fx)
+            info['n_force_calls'] += 1
+            info['fire_launches'] += 1
+            info['system_steps_evaluated'] += len(ids)
+            left = int(n_active.item())   # the one readback of the step
+            if left == 0:
+                break
+            if book.wants_repack(left, len(ids), repack_below):
+                act_h, st_h = torch.stack([active, n_steps]).cpu().numpy()
+                keep, rows = book.repack(pos, act_h, st_h)
+                rows_d, keep_d = torch.as_tensor(rows).to(dev), torch.as_tensor(keep).to(dev)
+                pos, vel, ty = pos[rows_d], vel[rows_d], ty[rows_d]   # (gathers copy: the stored slices keep the old buffer)
+                dt, alpha, n_pos, active, n_steps, fmax_sys = (t[keep_d] for t in (dt, alpha, n_pos, active, n_steps, fmax_sys))
+        act_h, st_h = torch.stack([active, n_steps]).cpu().numpy()
+        book.store(pos, act_h, st_h, only_finished=False)
+        info['n_repacks'] = book.n_repacks
+        final = torch.cat(book.positions)
+    return final, book.n_steps.copy(), book.converged.copy(), info
+
+
+def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: float = 0.05, steps: int = 500,
+                repack_below: float = 0.5, extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
+                **fire) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+    """Relax B structures at fixed cells with FIRE until every atom's force is below `fmax` (eV/A) or `steps` steps are done.
+
+    engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `build_batch_graph`; the
+    caller's arrays are not modified.  repack_below: when at most this fraction of the current batch is still active (and a
+    system has finished since the batch was built) the batch is rebuilt from the active systems; 0 never repacks.
+    extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [b+1] on the host, ids int64 [b]: the caller's
+    index of each system of the current batch) -> fp64 forces [N,3] added to the model's each step.  fire: FIRE_DEFAULTS
+    overrides.
+
+    Returns (results, info).  results[b]: the dict of SevenNetCalculator.compute_many from ONE batched evaluation of all B
+    systems at their final positions, plus `positions` [n,3] fp64, `converged` and `n_steps` (the moves made).  A system is
+    converged when the step kernel found its largest atomic force below fmax at the positions returned; one that reaches the
+    step cap is returned with converged = False.  info: n_force_calls (engine calls, the final evaluation included),
+    fire_launches (= loop iterations), system_steps_evaluated (systems in the batch, summed over the loop's engine calls),
+    n_repacks.  Invalid input raises ValueError before any device work."""
+    params = check_fire_params(fmax, steps, repack_below, fire)
+    types, positions, n_at, cells, pbcs = validate_relax_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
+                                                                n_atoms=n_atoms)
+    final, n_steps, converged, info = fire_loop(engine, types, positions, n_at, cells, pbcs, cutoff=cutoff, fmax=fmax, steps=steps,
+                                                repack_below=repack_below, params=params, extra=extra)
+    g = build_batch_graph(torch.as_tensor(types.astype(np.int32)).to(engine.dev), final, cells, pbcs, cutoff, engine.spec.num_species,
+                          n_atoms=n_at, device=engine.dev, species_rows=engine.needs_species_rows)
+    out = engine.compute(g, want_atomic_virial=want_atomic_virial)
+    info['n_force_calls'] += 1
+    results = batch_results(g, out, cells, want_atomic_virial)
+    return attach_relaxed(results, final, g.seg_ptr_host, n_steps, converged), info
+
+
+def attach_relaxed(results: List[Dict[str, Any]], final: torch.Tensor, seg_ptr_host, n_steps, converged) -> List[Dict[str, Any]]:
+    """`positions`, `converged` and `n_steps` into each system's results dict"""
+    pos_h = final.cpu().numpy()
+    for b, res in enumerate(results):
+        res['positions'] = pos_h[int(seg_ptr_host[b]):int(seg_ptr_host[b + 1])].copy()
+        res['converged'] = bool(converged[b])
+        res['n_steps'] = int(n_steps[b])
+    return results
