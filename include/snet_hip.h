@@ -237,6 +237,30 @@ int snet_conv_bwd_fused_sh(const snet_fused_plan *plan, const float *x, const fl
                            int64_t n_tiles, float scale, const float *g_out, float *g_xe, float *g_h2, const float *emb,
                            float *g_emb, float *g_sh, const float *x_rowmax, const float *g_rowmax, void *stream);
 int snet_fused_plan_has_mlp_tail(const snet_fused_plan *plan);
+/* ---- radial gradient by FORWARD TANGENT --------------------------------------------------------------------------------
+ * The radial branch of an edge is a function of ONE scalar, |r_e|: emb(|r|) -> h2 -> w = h2 W2.  So all the reverse pass needs of
+ * it is dE/d|r_e| = sum_k g_w[e,k] w'_e[k] with w'_e = h2'_p W2 and h2'_p = d h2_p / d|r| (one 64-float row per radial row and
+ * layer).  w' is a second product on the W2 fragments the reverse kernel reads for w anyway, its contraction with the fresh g_w
+ * tiles one multiply-add per register: the kernel then needs no operand split of g_w, no g_h2 = g_w W2^T products, no second W2
+ * image in LDS and no hidden-layer tail, and nothing is left for snet_edge_embed_bwd to do.
+ *   snet_edge_embed_tangent                  demb[n_rows, nb] = d emb / d|r| of row i's edge (edge_of_row[i]; NULL: edge i)
+ *   snet_radial_mlp_hidden_fwd_layers_tangent  snet_radial_mlp_hidden_fwd_layers (h2[l] bit for bit) plus h2d[l][R,64] = d h2 / d|r|;
+ *                                            every radial activation, any n_basis <= 32
+ *   snet_conv_bwd_fused_tangent              snet_conv_bwd_fused without g_h2 / emb / g_emb: g_vec[E,3] ACCUMULATES the spherical part
+ *                                            (as before) AND dE/d|r_e| r_e / |r_e|; g_xe as snet_conv_bwd_fused writes it, bit for bit.
+ *                                            h2d rows are read like h2 rows (w_row); edge_vec[E,3] as snet_edge_embed_fwd took it. */
+ /* snet_fused_plan_prefers_tangent() != 0: this shape's reverse pass is faster in tangent mode (every shape has both kernels; the
+ * lmax-3 middle-layer shapes, which sit at the register limit, keep the reverse-mode one).  Both hosts follow it per layer. */
+int snet_fused_plan_prefers_tangent(const snet_fused_plan *plan);
+int snet_edge_embed_tangent(const snet_edge_params *p_host, const float *coeffs_host, const float *edge_vec,
+                            const int32_t *edge_of_row, int64_t n_rows, float *demb, void *stream);
+int snet_radial_mlp_hidden_fwd_layers_tangent(const snet_mlp_plan *const *plans, int32_t n_layers, const float *emb, const float *demb,
+                                              int64_t n_rows, float *const *h2, float *const *h2d, void *stream);
+int snet_conv_bwd_fused_tangent(const snet_fused_plan *plan, const float *x, const float *sh, const float *dsh, const float *h2,
+                                const float *h2d, const int32_t *w_row, const int32_t *row_ptr, const int32_t *src,
+                                const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles, float scale, const float *g_out,
+                                float *g_xe, const float *edge_vec, float *g_vec, const float *x_rowmax, const float *g_rowmax,
+                                void *stream);
 /* g_xe[E,dx] of snet_conv_bwd_fused is an intermediate with its own row layout: the 16-channel chunks of a row are stored in
  * the order the kernel produces them ([x block][channel tile][component]: each (block, tile) writes one contiguous run per
  * edge instead of half cache lines).  chunk_pos[s] (dx / 16 entries, host) = position of standard chunk s in the row;

@@ -86,6 +86,13 @@ SIGNATURES = {
                                          c_i32p, C.c_int64, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                          c_stream]),
     'snet_fused_plan_has_mlp_tail': (C.c_int, [C.c_void_p]),
+    'snet_fused_plan_prefers_tangent': (C.c_int, [C.c_void_p]),
+    'snet_edge_embed_tangent': (C.c_int, [C.POINTER(EdgeParams), C.POINTER(C.c_float), c_f32p, c_i32p, C.c_int64, c_f32p, c_stream]),
+    'snet_radial_mlp_hidden_fwd_layers_tangent': (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, c_f32p, c_f32p, C.c_int64,
+                                                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_stream]),
+    'snet_conv_bwd_fused_tangent': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                              c_i32p, C.c_int64, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                              c_stream]),
     'snet_fused_plan_gxe_chunks': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     'snet_segment_sum_rows_chunked': (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int64, C.c_int32, c_i32p, c_f32p, c_stream]),
     'snet_edge_vectors': (C.c_int, [c_f64p, c_i32p, c_i32p, c_f64p, C.c_int64, c_f32p, c_stream]),

@@ -161,8 +161,12 @@ def build(jobs: int = 0, force: bool = False, extra_configs=(), verbose: bool = 
             codegen.write_if_changed(fpath, codegen_fused.gen_conv_fused(spec))
             sources.append(fpath)
             keep.add(os.path.basename(fpath))
+            tpath = os.path.join(GEN, f'convft_{tag}.hip')   # ... and the tangent-mode reverse kernel: another one
+            codegen.write_if_changed(tpath, codegen_fused.gen_conv_fused_tangent(spec))
+            sources.append(tpath)
+            keep.add(os.path.basename(tpath))
     for f in os.listdir(GEN):  # drop stale generated shapes
-        if (f.startswith('conv_') or f.startswith('convf_') or f.startswith('_conv')) and f not in keep:
+        if (f.startswith('conv_') or f.startswith('convf_') or f.startswith('convft_') or f.startswith('_conv')) and f not in keep:
             os.remove(os.path.join(GEN, f))
     jobs = jobs or min(16, os.cpu_count() or 4)
     if verbose:

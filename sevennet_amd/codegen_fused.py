@@ -244,8 +244,11 @@ class _Gen:
     (prologue / block top / sub-step / block end / hidden-layer tail / epilogue), forward kernel (prologue / pass top / block),
     launchers."""
 
-    def __init__(self, spec: ConvSpec):
+    def __init__(self, spec: ConvSpec, tangent: bool = False):
         self.spec = spec
+        # tangent: generate the TANGENT-MODE reverse kernel (`gen_conv_fused_tangent`, its own translation unit convft_<tag>.hip) instead
+        # of the kernels of `gen_conv_fused`, whose text does not depend on anything below that reads this flag
+        self.TG = bool(tangent)
         tag = self.tag = spec.tag
         # default configuration of the two kernels: (waves per workgroup, direct global->LDS staging, waves per SIMD the
         # register allocation targets); SNET_CODEGEN_OPTS="fexp=<tag>" adds every combination for one shape, selected at
@@ -273,6 +276,8 @@ class _Gen:
         self.FRSB = int(OPTS.get('frsb', 0))   # scheduler fence between the rows of a forward body with >= frsb Clebsch-Gordan entries (0: none)
         self._reverse_decisions()
         self._forward_decisions()
+        if self.TG:   # (the phase-stamp instruments live in the reverse-mode translation unit only)
+            self.stamped = self.ST = self.STL = False
 
     # ---------------------------------------------------------------- decisions of the reverse kernel
     def _reverse_decisions(self):
@@ -348,6 +353,12 @@ class _Gen:
         # "around them" is measured on a kernel that runs close to the shipped one
         self.STL = OPTS.get('stampl') == self.tag
         self.ST = OPTS.get('stamp') == self.tag or self.STL
+        # Tangent mode (radial gradient by forward tangent): what the hosts are told to use for this shape.  It trades the 16 g_h2
+        # accumulators for the 8 NT registers of the second B operand h2' plus w' and its partial sums; the shapes that sit at 256
+        # registers already (lmax-3 middle layers: live > 200) pay for that with spills and ran 4 .. 5 % SLOWER in the step (same box:
+        # sevennet_l3i5 45.1 -> 47.5 ms, sevennet_mf_ompa 44.4 -> 46.5 ms with tangent mode everywhere), so they keep the reverse-mode
+        # kernel.  SNET_CODEGEN_OPTS=tgpref=0 / 1 forces it.
+        self.TGPREF = bool(int(OPTS['tgpref'])) if 'tgpref' in OPTS else live <= 200
 
     def block_info(self, ci):
         """(x block, member tiles per block, blocks, 2 l1 + 1, no register prefetch of the next block's rows) of reverse block ci"""
@@ -608,8 +619,14 @@ def _rev_prologue(cx: _Gen):
     if cx.stamped:
         A('constexpr int SNET_STAMP_TILES = 1 << 18;')
         A('__device__ unsigned snet_stamps[16 * SNET_STAMP_TILES];   // one row per tile: no atomics (2.7 M atomics on 16 hot words stalled the whole chip)')
+    TG = cx.TG
+    if TG:
+        A('// TANGENT MODE of the reverse kernel: the radial gradient dE/d|r_e| = sum_k g_w[e, k] w\'_e[k] with w\'_e = h2\' W2, h2\' = d h2 / d|r| of')
+        A('// the edge\'s radial row (tail.h2d).  w\' is a second product on the A fragments of w, its contraction with the fresh g_w tiles one')
+        A('// multiply-add per register.  No operand split of g_w, no g_h2 products, no second W2 image in the slab, no hidden-layer tail, no')
+        A('// g_emb: the sum goes, along r_e / |r_e|, straight into the g_vec row the kernel writes anyway.')
     A('template <int NT, bool F16, int NWV, bool GLDS, int OCC, bool GX>')
-    A(f'__global__ __launch_bounds__(64 * NWV, OCC) void conv_bwdf_{tag}(const float *__restrict__ x, const float *__restrict__ sh,')
+    A(f'__global__ __launch_bounds__(64 * NWV, OCC) void conv_bwdf{"t" if TG else ""}_{tag}(const float *__restrict__ x, const float *__restrict__ sh,')
     A('    const float *__restrict__ dsh, const float *__restrict__ h2, const int32_t *__restrict__ w_row,')
     A('    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ src, const int32_t *__restrict__ tile_ptr,')
     A('    const int32_t *__restrict__ tile_node, int n_tiles, const u32x4 *__restrict__ slabs, float scale,')
@@ -618,8 +635,12 @@ def _rev_prologue(cx: _Gen):
     A('  // diag: always 0 in production (bit 0 also serves as the opaque branch condition around the tensor-product bodies);')
     A('  // kernel-tuning builds: 1 skip the tensor product, 2 skip the g_h2 products, 4 skip the w products, 8 skip the')
     A('  // g_out loads, 16 skip the g_xe stores -- timing decomposition, results are then garbage')
-    A('  constexpr int LPS = 8 * NT, NTH = 64 * NWV, NST = (LPS * 64 + NTH - 1) / NTH, GLN = 1;  // 1-KB fragment lines per sub-step; sub-steps per slab')
-    A('  __shared__ u32x4 slab[2][GLN * LPS * 64];')
+    if TG:   # (the stream keeps LPS lines per sub-step; only its w half, LW lines, is staged in LDS)
+        A('  constexpr int LPS = 8 * NT, LW = 4 * NT, NTH = 64 * NWV, NST = (LW * 64 + NTH - 1) / NTH, GLN = 1;  // 1-KB fragment lines per sub-step in the stream / staged; sub-steps per slab')
+        A('  __shared__ u32x4 slab[2][GLN * LW * 64];')
+    else:
+        A('  constexpr int LPS = 8 * NT, NTH = 64 * NWV, NST = (LPS * 64 + NTH - 1) / NTH, GLN = 1;  // 1-KB fragment lines per sub-step; sub-steps per slab')
+        A('  __shared__ u32x4 slab[2][GLN * LPS * 64];')
     A('  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: scalar address arithmetic)')
     A('  const int j = lane & 15, g = lane >> 4;')
     if ST:
@@ -639,7 +660,7 @@ def _rev_prologue(cx: _Gen):
     # Prologue order: every load is requested as soon as its address is known -- the first weight slab at once, the
     # node's g_out entries with the row pointers, the first source rows with h2 -- so the tile pays four dependent
     # memory latencies (tile -> node -> edge -> rows) instead of seven before its first matrix product.
-    _emit_staging(A, 'LPS')
+    _emit_staging(A, 'LW' if TG else 'LPS')
     A('  stage_load(0, 0);')
     A('  const int t_raw = snet::xcd_node(blockIdx.x, gridDim.x) * NWV + wave;')
     A('  const bool live = t_raw < n_tiles;')
@@ -728,9 +749,35 @@ def _rev_prologue(cx: _Gen):
     A('    hb[0] = splitn8<NT, F16>(hv[0]);')
     A('    hb[1] = splitn8<NT, F16>(hv[1]);')
     A('  }')
-    A('  f32x4 ga[4];  // g_h2^T[k = 16 m + 4 g + r][edge]')
-    A('#pragma unroll')
-    A('  for (int m = 0; m < 4; ++m) ga[m] = f32x4{0.f, 0.f, 0.f, 0.f};')
+    if TG:
+        A('  SplitN<NT> hdb[2];   // h2\'^T as a second B operand, with its OWN tile scale (|h2\'| is not bounded by |h2|)')
+        A('  float hd_unsc = 1.f;')
+        A('  f32x4 gt = f32x4{0.f, 0.f, 0.f, 0.f};   // per-lane partial sums of g_w w\' (times 2^(kg + kd + w2_exp) with fp16 terms)')
+        A('  {')
+        A('    float hv[2][8];')
+        A('#pragma unroll')
+        A('    for (int q = 0; q < 2; ++q) {')
+        A('      const f32x4 lo4 = *reinterpret_cast<const f32x4 *>(tail.h2d + (size_t)wr * 64 + 32 * q + 8 * g);')
+        A('      const f32x4 hi4 = *reinterpret_cast<const f32x4 *>(tail.h2d + (size_t)wr * 64 + 32 * q + 8 * g + 4);')
+        A('#pragma unroll')
+        A('      for (int i = 0; i < 4; ++i) { hv[q][i] = lo4[i]; hv[q][4 + i] = hi4[i]; }')
+        A('    }')
+        A('    if constexpr (F16) {')
+        A('      const int kd = min(60, snet::F16_TOP - snet::bound_exp(snet::wave_max(fmaxf(snet::max8(hv[0]), snet::max8(hv[1])))));')
+        A('      const float sc = snet::pow2f(kd);')
+        A('#pragma unroll')
+        A('      for (int q = 0; q < 2; ++q)')
+        A('#pragma unroll')
+        A('        for (int i = 0; i < 8; ++i) hv[q][i] *= sc;')
+        A('      hd_unsc = snet::pow2f(-kd);')
+        A('    }')
+        A('    hdb[0] = splitn8<NT, F16>(hv[0]);')
+        A('    hdb[1] = splitn8<NT, F16>(hv[1]);')
+        A('  }')
+    else:
+        A('  f32x4 ga[4];  // g_h2^T[k = 16 m + 4 g + r][edge]')
+        A('#pragma unroll')
+        A('  for (int m = 0; m < 4; ++m) ga[m] = f32x4{0.f, 0.f, 0.f, 0.f};')
     if cx.PKGY:   # packed bodies keep two partial sums of dE/dY per component (added in the epilogue)
         A('  f32x2 gy[NSH];')
         A('#pragma unroll')
@@ -828,7 +875,7 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
     operand split of the two g_w tiles and  g_h2^T += W2 g_w^T;  the next sub-step's slab is parked, one workgroup barrier"""
     A, spec, exp, ST, STL, HOIST = cx.A, cx.spec, cx.exp, cx.ST, cx.STL, cx.HOIST
     S, g_row = cx.S, cx.g_row
-    U = cx.bsched[ci]['U']
+    U, TG = cx.bsched[ci]['U'], cx.TG
     A('    {')
     if not (HOIST and si_ == 0):   # (first sub-step of a block: requested at the end of the previous block / the prologue)
         A('      if (sidx + 1 < NSUB' + (' && !(diag & 32)' if exp else '') + ') stage_load(sidx + 1, (buf ^ 1));')
@@ -845,7 +892,7 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
         p = spec.paths[pi]
         d3 = 2 * p.l3 + 1
         A(f'      {{  // tile {tp}: path {pi}, channel tile {U} cb + {u}')
-        A('        f32x4 wv = f32x4{0.f, 0.f, 0.f, 0.f};')
+        A('        f32x4 wv = f32x4{0.f, 0.f, 0.f, 0.f}' + (', wd = wv;' if TG else ';'))
         if exp:
             A('        if (diag & 4) wv = f32x4{yl[0], yl[16], yl[32], yl[48]}; else')
         A('#pragma unroll')
@@ -854,6 +901,8 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
         A('#pragma unroll')
         A(f'          for (int tm = 0; tm < NT; ++tm) a[tm] = as_bf16x8(sl[(({tp} * 2 + q) * NT + tm) * 64 + lane]);')
         A('          wv = mfma16_split<NT, F16>(a, hb[q], wv);')
+        if TG:
+            A('          wd = mfma16_split<NT, F16>(a, hdb[q], wd);   // w\' on the same A fragments')
         A('        }')
         if ST and not STL:
             A('        asm volatile("" :: "v"(wv[0]), "v"(wv[3]));')
@@ -874,19 +923,22 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
         A(f'        if (!(diag & 1)) bwdf_p{pi}<GX>(xr[{u}], ys, wv, G, gw{tp}, gy, gx[{u}]);')
         if ST and not STL:
             A(f'        asm volatile("" :: "v"(gw{tp}[0]), "v"(gw{tp}[3]));')
+        if TG:
+            A(f'        gt = __builtin_elementwise_fma(gw{tp}, wd, gt);')
         S(4 + 2 * tp, '        ')
         A('      }')
-    A('      float v[8] = {gw0[0], gw0[1], gw0[2], gw0[3], gw1[0], gw1[1], gw1[2], gw1[3]};')
-    A('      const SplitN<NT> b = splitn8<NT, F16>(v);')
-    if exp:
-        A('      if (diag & 2) ga[0] += f32x4{v[0], v[1], v[4], v[5]}; else')
-    A('#pragma unroll')
-    A('      for (int m = 0; m < 4; ++m) {')
-    A('        bf16x8 a[NT];')
-    A('#pragma unroll')
-    A('        for (int tm = 0; tm < NT; ++tm) a[tm] = as_bf16x8(sl[(4 * NT + m * NT + tm) * 64 + lane]);')
-    A('        ga[m] = mfma16_split<NT, F16>(a, b, ga[m]);')
-    A('      }')
+    if not TG:
+        A('      float v[8] = {gw0[0], gw0[1], gw0[2], gw0[3], gw1[0], gw1[1], gw1[2], gw1[3]};')
+        A('      const SplitN<NT> b = splitn8<NT, F16>(v);')
+        if exp:
+            A('      if (diag & 2) ga[0] += f32x4{v[0], v[1], v[4], v[5]}; else')
+        A('#pragma unroll')
+        A('      for (int m = 0; m < 4; ++m) {')
+        A('        bf16x8 a[NT];')
+        A('#pragma unroll')
+        A('        for (int tm = 0; tm < NT; ++tm) a[tm] = as_bf16x8(sl[(4 * NT + m * NT + tm) * 64 + lane]);')
+        A('        ga[m] = mfma16_split<NT, F16>(a, b, ga[m]);')
+        A('      }')
     if ST and not STL:
         A('      asm volatile("" :: "v"(ga[0][0]), "v"(ga[1][0]), "v"(ga[2][0]), "v"(ga[3][0]));')
     S(7)
@@ -963,6 +1015,8 @@ def _rev_tail(cx: _Gen):
             A(f'    for (int q = 4 * g; q < {mul_d * (2 * l_d + 1)}; q += 16)')
             A(f'      *reinterpret_cast<f32x4 *>(g_xe + (size_t)e * DX + {offs_x[i]} + q) = f32x4{{0.f, 0.f, 0.f, 0.f}};')
         A('  }')
+    if cx.TG:   # no g_h2, nothing of the radial MLP to reverse
+        return
     A('  if constexpr (F16) {  // back to g_h2 itself')
     A('#pragma unroll')
     A('    for (int m = 0; m < 4; ++m) ga[m] *= g_unsc;')
@@ -1161,6 +1215,20 @@ def _rev_epilogue(cx: _Gen):
     A('    float *o = g_vec + (size_t)e * 3;')
     A('    o[0] += t0 * gx_fix; o[1] += t1 * gx_fix; o[2] += t2 * gx_fix;   // (gx_fix: the bodies\' common factor, see the prologue)')
     A('  }')
+    if cx.TG:   # radial part: dE/d|r_e|, summed over the edge's four lanes like dE/dY, along the unit vector of the edge
+        A('  {')
+        A('    float gr = (gt[0] + gt[1]) + (gt[2] + gt[3]);')
+        A('    gr = snet::swap_add16(gr, gr);')
+        A('    gr = snet::swap_add32(gr, gr);')
+        A('    if (valid && g == 0) {')
+        A('      gr = gr * g_unsc * hd_unsc;   // g_w carried 2^kg, w\' 2^(kd + w2_exp) (fp16 terms; 1 otherwise)')
+        A('      const float *v_ = tail.edge_vec + (size_t)e * 3;')
+        A('      const float vx = v_[0], vy = v_[1], vz = v_[2];')
+        A('      const float ir = 1.f / sqrtf(vx * vx + vy * vy + vz * vz);')
+        A('      float *o = g_vec + (size_t)e * 3;')
+        A('      o[0] += gr * vx * ir; o[1] += gr * vy * ir; o[2] += gr * vz * ir;')
+        A('    }')
+        A('  }')
     if ST:
         S(13, '  ')
         A('  if (lane == 0 && live && t_raw < SNET_STAMP_TILES) {')
@@ -1501,7 +1569,8 @@ def _variants(exp, default, fwd=False):
 
 
 def _emit_launch_bwd(cx: _Gen):
-    A, tag, exp, def_b, bwd_cfg = cx.A, cx.tag, cx.exp, cx.def_b, cx.bwd_cfg
+    A, exp, def_b, bwd_cfg = cx.A, cx.exp, cx.def_b, cx.bwd_cfg
+    tag = ('t_' if cx.TG else '_') + cx.tag   # (the tangent-mode kernel: conv_bwdft_<tag>, same configurations, launch_bwd_tangent)
     A('template <int NT, bool F16, int NWV, bool GLDS, int OCC>')
     A('void launch_bwd_t(const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,')
     A('                  const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles,')
@@ -1513,13 +1582,13 @@ def _emit_launch_bwd(cx: _Gen):
     A('  // launches without a g_xe output (first layer, last layer with the transposed convolution) take the instantiation that does not form')
     A('  // the source-row gradient: its multiply-adds and its 4 U d1 registers per lane are gone, not just its stores')
     A('  if (g_xe != nullptr)')
-    A(f'    conv_bwdf_{tag}<NT, F16, NWV, GLDS, OCC, true><<<dim3(grid), dim3(64 * NWV), 0, st>>>(x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node,')
+    A(f'    conv_bwdf{tag}<NT, F16, NWV, GLDS, OCC, true><<<dim3(grid), dim3(64 * NWV), 0, st>>>(x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node,')
     A('        (int)n_tiles, static_cast<const u32x4 *>(slabs), scale, g_out, g_xe, g_h2, g_vec, tail, diag);')
     A('  else')
-    A(f'    conv_bwdf_{tag}<NT, F16, NWV, GLDS, OCC, false><<<dim3(grid), dim3(64 * NWV), 0, st>>>(x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node,')
+    A(f'    conv_bwdf{tag}<NT, F16, NWV, GLDS, OCC, false><<<dim3(grid), dim3(64 * NWV), 0, st>>>(x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node,')
     A('        (int)n_tiles, static_cast<const u32x4 *>(slabs), scale, g_out, g_xe, g_h2, g_vec, tail, diag);')
     A('}')
-    A('void launch_bwd(int nt, const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,')
+    A(f'void launch_bwd{"_tangent" if cx.TG else ""}(int nt, const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,')
     A('                const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles,')
     A('                const void *slabs, float scale, const float *g_out, float *g_xe, float *g_h2, float *g_vec, snet::FusedTail tail, hipStream_t st) {')
     args_b = 'x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, slabs, scale, g_out, g_xe, g_h2, g_vec, tail, st'
@@ -1574,6 +1643,11 @@ def _emit_launch_fwd(cx: _Gen):
 
 def _emit_registration(cx: _Gen):
     A, tag, XT, cols_rev = cx.A, cx.tag, cx.XT, cx.cols_b
+    if cx.TG:
+        A(f'const snet::FusedTangentKernels kernels = {{"{tag}", {1 if cx.TGPREF else 0}, launch_bwd_tangent}};')
+        A('const snet::FusedTangentRegistrar registrar(&kernels);')
+        A('}  // namespace')
+        return
     A(f'const snet::FusedKernels kernels = {{"{tag}", DX, DOUT, NSH, WN, NS, SUB_COLS, {len(cols_rev)}, SUB_COLS_B, GXE_CHUNK, launch_bwd, launch_fwd, {1 if XT else 0}}};')
     A('const snet::FusedRegistrar registrar(&kernels);')
     A('}  // namespace')
@@ -1597,6 +1671,17 @@ def _emit_registration(cx: _Gen):
         A('  if (reset) { void *dev = nullptr; if (hipGetSymbolAddress(&dev, HIP_SYMBOL(snet_stamps)) != hipSuccess || hipMemset(dev, 0, bytes) != hipSuccess) return 1; }')
         A('  return 0;')
         A('}')
+
+
+def gen_conv_fused_tangent(spec: ConvSpec) -> str:
+    """the tangent-mode reverse kernel of a fused shape (translation unit convft_<tag>.hip, registered beside convf_<tag>.hip's kernels)"""
+    cx = _Gen(spec, tangent=True)
+    _emit_header(cx)
+    _emit_path_functions(cx)
+    _emit_reverse_kernel(cx)
+    _emit_launch_bwd(cx)
+    _emit_registration(cx)
+    return '\n'.join(cx.L) + '\n'
 
 
 def gen_conv_fused(spec: ConvSpec) -> str:

@@ -29,6 +29,16 @@ const FusedKernels *find_fused(const char *tag) {
     if (std::string(k->tag) == tag) return k;
   return nullptr;
 }
+static std::vector<const FusedTangentKernels *> &fused_tangent_registry() {
+  static std::vector<const FusedTangentKernels *> r;
+  return r;
+}
+void register_fused_tangent(const FusedTangentKernels *k) { fused_tangent_registry().push_back(k); }
+const FusedTangentKernels *find_fused_tangent(const char *tag) {
+  for (const FusedTangentKernels *k : fused_tangent_registry())
+    if (std::string(k->tag) == tag) return k;
+  return nullptr;
+}
 
 // Small scratch for deterministic two-stage reductions, per host thread and device (grown on
 // demand, never shrunk).  Per-thread because the partial-sum kernel and its final-sum kernel are
@@ -58,6 +68,7 @@ struct snet_conv_plan {
 };
 struct snet_fused_plan {
   const snet::FusedKernels *k;
+  const snet::FusedTangentKernels *kt;  // the shape's tangent-mode reverse kernel (nullptr: not compiled in)
   int terms;
   void *slabs;    // device: W2 as pre-split MFMA fragments in the FORWARD kernel's sub-step order
   void *slabs_b;  // the same in the REVERSE kernel's order, then the hidden-layer tail
@@ -166,7 +177,7 @@ int snet_fused_plan_create(const snet_conv_plan *plan, const snet_mlp_plan *mlp,
     snet::set_error("snet_fused_plan_create: device allocation / upload of the W2 fragment stream failed");
     return 1;
   }
-  *out = new snet_fused_plan{k, terms, dev, dev_b, hid, {exps[0], exps[1], exps[2]}};
+  *out = new snet_fused_plan{k, snet::find_fused_tangent(plan->k->tag), terms, dev, dev_b, hid, {exps[0], exps[1], exps[2]}};
   return 0;
 }
 int snet_fused_plan_tile_mode(const snet_fused_plan *p) { return p ? p->k->tile_mode : 0; }
@@ -214,7 +225,7 @@ static int conv_bwd_fused_impl(const char *who, const snet_fused_plan *fp, const
   SNET_REQUIRE((dsh != nullptr) == (g_vec != nullptr), std::string(who) + ": dsh and g_vec go together");
   SNET_REQUIRE(g_vec != nullptr || g_sh != nullptr, std::string(who) + ": no output for the harmonics' gradient (g_vec or g_sh)");
   const snet::FusedTail tail{emb, g_emb, fp->hidden.nb, fp->hidden.act, fp->hidden.cst, fp->exps[0], fp->exps[1], fp->exps[2],
-                             x_rowmax, g_rowmax, g_sh};
+                             x_rowmax, g_rowmax, g_sh, nullptr, nullptr};
   fp->k->bwd(fp->terms, x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, fp->slabs_b, scale, g_out,
              g_xe, g_h2, g_vec, tail, static_cast<hipStream_t>(stream));
   SNET_CHECK_LAUNCH(who);
@@ -227,6 +238,32 @@ int snet_conv_bwd_fused(const snet_fused_plan *fp, const float *x, const float *
                         const float *g_rowmax, void *stream) {
   return conv_bwd_fused_impl("snet_conv_bwd_fused", fp, x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, scale, g_out,
                              g_xe, g_h2, emb, g_emb, g_vec, nullptr, x_rowmax, g_rowmax, stream);
+}
+int snet_fused_plan_prefers_tangent(const snet_fused_plan *fp) {
+  return fp != nullptr && fp->kt != nullptr && fp->kt->tangent_pref != 0;
+}
+int snet_conv_bwd_fused_tangent(const snet_fused_plan *fp, const float *x, const float *sh, const float *dsh, const float *h2,
+                                const float *h2d, const int32_t *w_row, const int32_t *row_ptr, const int32_t *src,
+                                const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles, float scale, const float *g_out,
+                                float *g_xe, const float *edge_vec, float *g_vec, const float *x_rowmax, const float *g_rowmax,
+                                void *stream) {
+  SNET_REQUIRE(fp != nullptr, "snet_conv_bwd_fused_tangent: null plan");
+  SNET_REQUIRE(fp->kt != nullptr, "snet_conv_bwd_fused_tangent: this shape's tangent-mode kernel is not compiled in");
+  SNET_REQUIRE(fp->terms != 4 || (x_rowmax != nullptr && g_rowmax != nullptr),
+               "snet_conv_bwd_fused_tangent: terms = 4 (fp16 operands) needs x_rowmax and g_rowmax (snet_row_absmax of x and g_out)");
+  SNET_REQUIRE(n_tiles < (1ll << 31), "snet_conv_bwd_fused_tangent: too many tiles");
+  if (n_tiles <= 0) return 0;
+  SNET_REQUIRE(tile_ptr != nullptr && tile_node != nullptr, "snet_conv_bwd_fused_tangent: null tile list");
+  SNET_REQUIRE(h2d != nullptr && edge_vec != nullptr && dsh != nullptr && g_vec != nullptr,
+               "snet_conv_bwd_fused_tangent: h2d, edge_vec, dsh and g_vec are required");
+  snet::FusedTail tail{nullptr, nullptr, fp->hidden.nb, fp->hidden.act, fp->hidden.cst, fp->exps[0], fp->exps[1], fp->exps[2],
+                       x_rowmax, g_rowmax, nullptr};
+  tail.h2d = h2d;
+  tail.edge_vec = edge_vec;
+  fp->kt->bwd(fp->terms, x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, fp->slabs_b, scale, g_out, g_xe, nullptr,
+              g_vec, tail, static_cast<hipStream_t>(stream));
+  SNET_CHECK_LAUNCH("snet_conv_bwd_fused_tangent");
+  return 0;
 }
 int snet_conv_bwd_fused_sh(const snet_fused_plan *fp, const float *x, const float *sh, const float *h2, const int32_t *w_row,
                            const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node,

@@ -79,6 +79,9 @@ struct FusedTail {
   // optional output (b1 plug-in: the reference's autograd needs the gradient with respect to edge_attr itself): g_sh[E, nsh]
   // OVERWRITTEN with dE/dY of every edge; NULL in the MD hosts, which take dE/d(edge_vec) through dsh / g_vec instead
   float *g_sh;
+  // tangent mode (bwd_tangent): h2d[rows of h2, 64] = d h2 / d|r| of the radial row (snet_radial_mlp_hidden_fwd_layers_tangent) and the
+  // edge vectors [E, 3]: the kernel forms dE/d|r_e| = sum_k g_w[e, k] (h2d W2)[k] itself and adds it, along r_e / |r_e|, to g_vec
+  const float *h2d, *edge_vec;
 };
 struct FusedKernels {
   const char *tag;
@@ -106,6 +109,22 @@ void register_fused(const FusedKernels *k);
 const FusedKernels *find_fused(const char *tag);
 struct FusedRegistrar {
   explicit FusedRegistrar(const FusedKernels *k) { register_fused(k); }
+};
+// the tangent-mode reverse kernel of a fused shape (generated convft_<tag>.hip, a translation unit of its own beside convf_<tag>.hip):
+// the radial gradient by forward tangent (tail.h2d, tail.edge_vec), no g_h2 / g_emb output (g_h2 is passed as NULL); g_vec[E,3] +=
+// receives the spherical AND the radial part.  Same weight stream, tile list and arguments as FusedKernels::bwd.
+struct FusedTangentKernels {
+  const char *tag;
+  int tangent_pref;  // 1: the hosts should run this shape's reverse pass in tangent mode (0: it is slower there -- register pressure)
+  void (*bwd)(int nt, const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,
+              const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node,
+              int64_t n_tiles, const void *slabs, float scale, const float *g_out, float *g_xe, float *g_h2,
+              float *g_vec, FusedTail tail, hipStream_t st);
+};
+void register_fused_tangent(const FusedTangentKernels *k);
+const FusedTangentKernels *find_fused_tangent(const char *tag);
+struct FusedTangentRegistrar {
+  explicit FusedTangentRegistrar(const FusedTangentKernels *k) { register_fused_tangent(k); }
 };
 // host copy of the radial MLP's pre-normalised last-layer weights W2'[64, wn] (row-major)
 const float *mlp_plan_w2_host(const snet_mlp_plan *plan);
@@ -248,6 +267,18 @@ __device__ __forceinline__ float sigmoid_fast(float z) { return __builtin_amdgcn
 __device__ __forceinline__ float act_fwd_fast(float z, int act) {
   if (act == 0) return z * sigmoid_fast(z);
   return act_fwd(z, act);
+}
+// value f = act_fwd_fast(z, act) (bit for bit) and derivative g of the same pre-activation: silu from one exponential, every other id
+// through act_fwd / act_grad (the tangent of the hidden radial layers)
+__device__ __forceinline__ void act_pair_radial(float z, int act, float &f, float &g) {
+  if (act == 0) {
+    const float s = sigmoid_fast(z);
+    f = z * s;
+    g = s * fmaf(z, 1.0f - s, 1.0f);
+  } else {
+    f = act_fwd(z, act);
+    g = act_grad(z, act);
+  }
 }
 // The gate kernels' forms (round 6): silu (0) and sigmoid (5) -- the scalar and gate activations of every SevenNet preset
 // (sevenn/_const.py:33-47 defaults) -- on hardware exp2 / rcp, every other id through libm.  The id differs per LANE there (a lane

@@ -156,6 +156,27 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(EdgeP P, const float *__r
   g_vec[3 * e + 2] = gz;
 }
 
+// d emb / d|r| of one radial row (row i: edge edge_of_row[i], or edge i without a map): the forward tangent of the radial basis --
+// the derivative edge_bwd_kernel contracts with g_emb, written out instead
+__global__ __launch_bounds__(256) void edge_tangent_kernel(EdgeP P, const float *__restrict__ vec, const int32_t *__restrict__ edge_of_row,
+                                                           int64_t n_rows, float *__restrict__ demb) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_rows) return;
+  const int64_t e = edge_of_row ? edge_of_row[i] : i;
+  const float x = vec[3 * e + 0], y = vec[3 * e + 1], z = vec[3 * e + 2];
+  const float r = sqrtf(x * x + y * y + z * z);
+  const float ir = 1.f / r;
+  float env, denv;
+  envelope(P, r, env, denv);
+  for (int k = 0; k < P.nb; ++k) {
+    float sn, cs;
+    sincosf(P.coeffs[k] * r, &sn, &cs);
+    const float f = sn * ir;
+    const float df = (P.coeffs[k] * cs - f) * ir;
+    demb[i * P.nb + k] = P.pref * (df * env + f * denv);
+  }
+}
+
 int prepare(const snet_edge_params *p, const float *coeffs_host, EdgeP &P) {
   SNET_REQUIRE(p != nullptr && coeffs_host != nullptr, "snet_edge_embed: null params");
   SNET_REQUIRE(p->n_basis >= 1 && p->n_basis <= 16, "snet_edge_embed: n_basis must be in 1..16");
@@ -257,5 +278,17 @@ extern "C" int snet_edge_embed_bwd(const snet_edge_params *p, const float *coeff
     default: edge_bwd_kernel<3><<<grid, 256, 0, st>>>(P, edge_vec, E, g_emb, g_sh, g_vec, accumulate); break;
   }
   SNET_CHECK_LAUNCH("snet_edge_embed_bwd");
+  return 0;
+}
+
+extern "C" int snet_edge_embed_tangent(const snet_edge_params *p, const float *coeffs, const float *edge_vec,
+                                       const int32_t *edge_of_row, int64_t n_rows, float *demb, void *stream) {
+  EdgeP P;
+  if (int rc = prepare(p, coeffs, P)) return rc;
+  if (n_rows <= 0) return 0;
+  SNET_REQUIRE(edge_vec != nullptr && demb != nullptr, "snet_edge_embed_tangent: null argument");
+  edge_tangent_kernel<<<(unsigned)((n_rows + 255) / 256), 256, 0, static_cast<hipStream_t>(stream)>>>(P, edge_vec, edge_of_row,
+                                                                                                       n_rows, demb);
+  SNET_CHECK_LAUNCH("snet_edge_embed_tangent");
   return 0;
 }

@@ -441,6 +441,7 @@ struct HiddenLayers {
   const float *W0[MAX_HIDDEN_LAYERS];
   const u32x4 *W1A[MAX_HIDDEN_LAYERS];
   float *h2[MAX_HIDDEN_LAYERS];
+  float *h2d[MAX_HIDDEN_LAYERS];   // tangent launch only: d h2 / d|r|
   float cst[MAX_HIDDEN_LAYERS];
   int act[MAX_HIDDEN_LAYERS];
   int n;
@@ -470,6 +471,91 @@ __global__ __launch_bounds__(256, 2) void radial_mlp_hidden_layers_kernel(const 
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = act_sel<ACT>(z2[t][4 * g + i], act) * cst;
         *reinterpret_cast<f32x4 *>(h2 + e_lane * H + 32 * t + 8 * g + 4 * half) = v;
+      }
+  }
+}
+
+// The same launch with the FORWARD TANGENT of the two hidden layers: the radial MLP's only input is the edge embedding, a function of
+// |r| alone, so  h2' = d h2 / d|r|  follows from  emb' = d emb / d|r|  (snet_edge_embed_tangent) by the chain rule, on the operands the
+// values use:  z1' = emb' W0,  a1' = cst act'(z1) z1',  z2' = a1' W1,  h2' = cst act'(z2) z2'.  The values take exactly the instructions of
+// radial_mlp_hidden_layers_kernel (h2 is bit-identical); value and derivative of an activation share one exponential (silu).
+template <int ACT>
+__device__ __forceinline__ void act_pair_sel(float z, int act, float &f, float &g) {
+  if constexpr (ACT >= 0) snet::act_pair_radial(z, ACT, f, g);
+  else snet::act_pair_radial(z, act, f, g);
+}
+
+template <int ACT, int NB>
+__global__ __launch_bounds__(256, 2) void radial_mlp_hidden_layers_tangent_kernel(const float *__restrict__ emb,
+                                                                               const float *__restrict__ demb, int64_t E, int nb,
+                                                                               HiddenLayers P) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, li = lane & 31;
+  const int64_t e_raw = ((int64_t)blockIdx.x * 4 + wave) * 32 + li;
+  const bool e_ok = e_raw < E;
+  const int64_t e_lane = e_ok ? e_raw : 0;
+  for (int l = 0; l < P.n; ++l) {
+    const int act = P.act[l];
+    const float cst = P.cst[l];
+    const float *__restrict__ W0 = P.W0[l];
+    const u32x4 *__restrict__ W1A = P.W1A[l];
+    f32x16 z1[2], z1d[2], z2[2], z2d[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) z1[t] = z1d[t] = z2[t] = z2d[t] = zero16();
+    auto l1_step = [&](int s, int n_basis) {
+      const int k = 2 * s + half;
+      const float b = (e_ok && k < n_basis) ? emb[e_lane * n_basis + k] : 0.f;
+      const float bd = (e_ok && k < n_basis) ? demb[e_lane * n_basis + k] : 0.f;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const float a = (k < n_basis) ? W0[k * H + 32 * t + li] : 0.f;
+        z1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, z1[t], 0, 0, 0);
+        z1d[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bd, z1d[t], 0, 0, 0);
+      }
+    };
+    if constexpr (NB > 0) {
+#pragma unroll
+      for (int s = 0; 2 * s < NB; ++s) l1_step(s, NB);
+    } else {
+      for (int s = 0; 2 * s < nb; ++s) l1_step(s, nb);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v[8], vd[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float f, g;
+        act_pair_sel<ACT>(z1[q >> 1][8 * (q & 1) + i], act, f, g);
+        v[i] = f * cst;
+        vd[i] = g * cst * z1d[q >> 1][8 * (q & 1) + i];
+      }
+      const Split3 b = split8(v), bd = split8(vd);
+#pragma unroll
+      for (int to = 0; to < 2; ++to) {
+        bf16x8 a[3];
+        load_frag3(W1A, to * 4 + q, lane, a);
+        z2[to] = mfma6(a, b, z2[to]);
+        z2d[to] = mfma6(a, bd, z2d[to]);
+      }
+    }
+    if (!e_ok) continue;
+    float *__restrict__ h2 = P.h2[l];
+    float *__restrict__ h2d = P.h2d[l];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 v, vd;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float f, d;
+          act_pair_sel<ACT>(z2[t][4 * g + i], act, f, d);
+          v[i] = f * cst;
+          vd[i] = d * cst * z2d[t][4 * g + i];
+        }
+        *reinterpret_cast<f32x4 *>(h2 + e_lane * H + 32 * t + 8 * g + 4 * half) = v;
+        *reinterpret_cast<f32x4 *>(h2d + e_lane * H + 32 * t + 8 * g + 4 * half) = vd;
       }
   }
 }
@@ -854,6 +940,35 @@ extern "C" int snet_radial_mlp_hidden_fwd_layers(const snet_mlp_plan *const *pla
   else if (silu) radial_mlp_hidden_layers_kernel<0, 0><<<(unsigned)grid, 256, 0, st>>>(emb, E, nb, P);
   else radial_mlp_hidden_layers_kernel<-1, 0><<<(unsigned)grid, 256, 0, st>>>(emb, E, nb, P);
   SNET_CHECK_LAUNCH("snet_radial_mlp_hidden_fwd_layers");
+  return 0;
+}
+
+extern "C" int snet_radial_mlp_hidden_fwd_layers_tangent(const snet_mlp_plan *const *plans, int32_t n_layers, const float *emb,
+                                                         const float *demb, int64_t E, float *const *h2, float *const *h2d, void *stream) {
+  SNET_REQUIRE(plans != nullptr && h2 != nullptr && h2d != nullptr, "snet_radial_mlp_hidden_fwd_layers_tangent: null argument");
+  SNET_REQUIRE(n_layers >= 1 && n_layers <= MAX_HIDDEN_LAYERS, "snet_radial_mlp_hidden_fwd_layers_tangent: 1 .. 8 layers per call");
+  HiddenLayers P{};
+  P.n = n_layers;
+  bool silu = true;
+  for (int l = 0; l < n_layers; ++l) {
+    const snet_mlp_plan *p = plans[l];
+    SNET_REQUIRE(p != nullptr, "snet_radial_mlp_hidden_fwd_layers_tangent: null plan");
+    SNET_REQUIRE(E <= 0 || (h2[l] != nullptr && h2d[l] != nullptr), "snet_radial_mlp_hidden_fwd_layers_tangent: null output");
+    SNET_REQUIRE(p->mode == 1, "snet_radial_mlp_hidden_fwd_layers_tangent: split-precision plans only (mode 1)");
+    SNET_REQUIRE(p->nb == plans[0]->nb, "snet_radial_mlp_hidden_fwd_layers_tangent: the layers must share the edge embedding (same n_basis)");
+    P.W0[l] = p->W0; P.W1A[l] = p->W1A; P.h2[l] = h2[l]; P.h2d[l] = h2d[l]; P.cst[l] = p->cst; P.act[l] = p->act;
+    silu = silu && p->act == 0;
+  }
+  if (E <= 0) return 0;
+  SNET_REQUIRE(emb != nullptr && demb != nullptr, "snet_radial_mlp_hidden_fwd_layers_tangent: null input");
+  const int64_t grid = (E + 127) / 128;
+  SNET_REQUIRE(grid < (1ll << 31), "snet_radial_mlp_hidden_fwd_layers_tangent: too many edges");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int nb = plans[0]->nb;
+  if (silu && nb == 8) radial_mlp_hidden_layers_tangent_kernel<0, 8><<<(unsigned)grid, 256, 0, st>>>(emb, demb, E, nb, P);
+  else if (silu) radial_mlp_hidden_layers_tangent_kernel<0, 0><<<(unsigned)grid, 256, 0, st>>>(emb, demb, E, nb, P);
+  else radial_mlp_hidden_layers_tangent_kernel<-1, 0><<<(unsigned)grid, 256, 0, st>>>(emb, demb, E, nb, P);
+  SNET_CHECK_LAUNCH("snet_radial_mlp_hidden_fwd_layers_tangent");
   return 0;
 }
 

@@ -669,8 +669,9 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   auto add = [&](size_t n) { need += ((n * 4 + 255) / 256) * 256; };
   size_t dmax = (size_t)m->d0, trans = 0;
   add((size_t)E * nb); add((size_t)E * nsh); add((size_t)E * nsh * 3); add((size_t)E * 3); add((size_t)E * nb);
-  add((size_t)WR * nb);
+  add((size_t)WR * nb); add((size_t)WR * nb);  // emb per radial row, its derivative with respect to |r|
   for (auto &L : m->layers) {
+    if (L.fused) add((size_t)WR * 64);  // h2' = d h2 / d|r| (tangent mode of the fused reverse kernel)
     dmax = dmax > (size_t)L.dout ? dmax : (size_t)L.dout;
     add((size_t)NT * L.dx); add(L.fused ? (size_t)WR * 64 : (size_t)WR * L.wn); add((size_t)N * L.gin);  // saved h, w | h2, y
     add((size_t)NT + 64);  // x_max (kept through the reverse pass)
@@ -712,11 +713,16 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   }
   float *x = A.f((size_t)NT * dmax), *x2 = A.f((size_t)NT * dmax);  // layer 0 reads the species tables, not x
 
-  struct Saved { float *h, *w, *y; };  // w: radial weights [WR, wn], or (fused layers) hidden activations h2 [WR, 64]
+  // w: radial weights [WR, wn], or (fused layers) hidden activations h2 [WR, 64] and wd = h2' = d h2 / d|r| [WR, 64]
+  struct Saved { float *h, *w, *y, *wd; };
   std::vector<Saved> saved(Lc);
+  bool all_tangent = true;   // every layer's radial gradient reaches g_vec inside its reverse kernel: no g_emb, no snet_edge_embed_bwd
   for (int t = 0; t < Lc; ++t) {
     saved[t].h = A.f((size_t)NT * m->layers[t].dx);
     saved[t].w = A.f(m->layers[t].fused ? (size_t)WR * 64 : (size_t)WR * m->layers[t].wn);
+    const bool tg = m->layers[t].fused != nullptr && snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0;
+    saved[t].wd = tg ? A.f((size_t)WR * 64) : nullptr;
+    all_tangent = all_tangent && tg;
     saved[t].y = A.f((size_t)N * m->layers[t].gin);
   }
   // topology-only work: rebuilt unless the cache holds it for exactly these index arrays
@@ -863,14 +869,26 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   const size_t mark = A.off;  // transient region starts here
 
   {  // hidden activations of every fused layer's radial MLP in one launch (the layers share the edge embedding; up to 8 per call)
+    // (with their forward tangent h2': the reverse kernels take the radial gradient from it)
+    // first the layers whose reverse kernel runs in tangent mode, then the others: the order of engine.py)
     const snet_mlp_plan *hp[8];
-    float *ho[8];
-    int nh = 0;
-    for (int t = 0; t <= Lc; ++t) {
-      if (t < Lc && m->layers[t].fused) { hp[nh] = m->layers[t].mlp_plan; ho[nh] = saved[t].w; ++nh; }
-      if (nh == 8 || (t == Lc && nh > 0)) {
-        if ((rc = snet_radial_mlp_hidden_fwd_layers(hp, nh, emb_w, WR, ho, st))) return rc;
-        nh = 0;
+    float *ho[8], *hd[8];
+    float *demb = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+      int nh = 0;
+      for (int t = 0; t <= Lc; ++t) {
+        if (t < Lc && m->layers[t].fused && (saved[t].wd != nullptr) == (pass == 0)) {
+          hp[nh] = m->layers[t].mlp_plan; ho[nh] = saved[t].w; hd[nh] = saved[t].wd; ++nh;
+        }
+        if (nh == 8 || (t == Lc && nh > 0)) {
+          if (pass == 0 && demb == nullptr) {
+            demb = A.f((size_t)WR * nb);
+            if ((rc = snet_edge_embed_tangent(&ep, m->coeffs.data(), edge_vec, pairs ? pair_edge : nullptr, WR, demb, st))) return rc;
+          }
+          if ((rc = pass == 0 ? snet_radial_mlp_hidden_fwd_layers_tangent(hp, nh, emb_w, demb, WR, ho, hd, st)
+                              : snet_radial_mlp_hidden_fwd_layers(hp, nh, emb_w, WR, ho, st))) return rc;
+          nh = 0;
+        }
       }
     }
   }
@@ -969,7 +987,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     if ((rc = snet_readout_grad(m->ro_v, m->ro1.dim_in, types, m->scale, m->n_scale, N, g_x, st))) return rc;
   }
   SNET_REQUIRE(hipMemsetAsync(g_vec, 0, (size_t)E * 3 * 4, st) == hipSuccess &&
-                   hipMemsetAsync(g_emb, 0, (size_t)E * nb * 4, st) == hipSuccess,
+                   (all_tangent || hipMemsetAsync(g_emb, 0, (size_t)E * nb * 4, st) == hipSuccess),
                "snet_model_eval: memset failed");
   // fp16 operands of the fused reverse kernels: the source-row bounds of all layers from one launch (up to 8 matrices per call)
   std::vector<float *> x_max_of((size_t)Lc, nullptr);
@@ -1004,12 +1022,17 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     if ((rc = run_linear(m, L.si2, g_y, g_m, N, true, false, st))) return rc;
     const bool transposed = t > 0 && L.tfused != nullptr && E > 0;
     float *g_xe = t > 0 && !transposed ? A.f((size_t)E * L.dx) : nullptr;
-    if (L.fused) {  // g_w is contracted with W2^T inside the kernel; with the hidden-layer tail not even g_h2 leaves it
-      const bool tail = snet_fused_plan_has_mlp_tail(L.fused) != 0;
+    if (L.fused) {  // g_w is contracted inside the kernel: with w' = h2' W2 (tangent mode: the radial gradient lands in g_vec), or with
+      // W2^T -- and with the hidden-layer tail not even g_h2 leaves it
+      const bool tg = saved[t].wd != nullptr;
+      const bool tail = tg || snet_fused_plan_has_mlp_tail(L.fused) != 0;   // nothing of the radial branch left to reverse afterwards
       float *g_h2 = tail ? nullptr : A.f((size_t)E * 64);
       float *x_max = x_max_of[t];   // (bounds of every edge's g_w, see snet_row_absmax; computed before the layer loop)
       auto bwd_tiles = [&](const int32_t *tp, const int32_t *tn, int64_t nt) -> int {
         if (E <= 0 || nt <= 0) return 0;
+        if (tg)
+          return snet_conv_bwd_fused_tangent(L.fused, saved[t].h, sh, dsh, saved[t].w, saved[t].wd, pairs ? w_row : nullptr, row_ptr, src,
+                                             tp, tn, nt, L.conv_scale, g_m, g_xe, edge_vec, g_vec, x_max, g_max, st);
         return snet_conv_bwd_fused(L.fused, saved[t].h, sh, dsh, saved[t].w, pairs ? w_row : nullptr, row_ptr, src, tp, tn, nt,
                                    L.conv_scale, g_m, g_xe, g_h2, tail ? emb : nullptr, tail ? g_emb : nullptr, g_vec, x_max, g_max, st);
       };
@@ -1103,7 +1126,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   for (int b = 0; b < 2; ++b)
     if (gw_busy[b])
       SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_bwd[b], 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-  if ((rc = snet_edge_embed_bwd(&ep, m->coeffs.data(), edge_vec, E, g_emb, nullptr, g_vec, 1, st))) return rc;
+  if (!all_tangent && (rc = snet_edge_embed_bwd(&ep, m->coeffs.data(), edge_vec, E, g_emb, nullptr, g_vec, 1, st))) return rc;
   A.off = mark2;
   float *F = forces ? forces : A.f((size_t)NT * 3);
   if ((rc = snet_edge_force(g_vec, edge_vec, row_ptr, col_ptr, eperm, NT, E, F, virial_atom, virial, st))) return rc;

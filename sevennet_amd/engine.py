@@ -300,7 +300,7 @@ class HipForceEngine:
     def __init__(self, config: dict, state_dict: Dict[str, np.ndarray], device='cuda:0', mlp_mode: str = 'bf16x6',
                  linear_mode: str = 'bf16x6', fused='auto', fused_terms='f16x3', modal=None, overlap: bool = True,
                  mlp_tail: bool = True, transposed_conv: bool = True, species_tables: bool = True,
-                 fold_readout: bool = True):
+                 fold_readout: bool = True, tangent: bool = True):
         """mlp_mode / linear_mode: 'bf16x6' (split-precision MFMA, fp32-class accuracy, default) or
         'fp32' (exact fp32 MFMA) for the fused radial MLP / the node-level equivariant linears.
         fused: 'auto' (default) / True / False / 'fwd' / 'bwd' -- run the radial MLP's last layer INSIDE the
@@ -330,6 +330,8 @@ class HipForceEngine:
         GEMMs, kept for A/B measurements).
         fold_readout: the two readout linears as one fp64-folded vector, per-atom dot product and rescale in fp64
         (snet_readout_energy) instead of two GEMMs + snet_rescale_reduce (False: the GEMMs, for A/B measurements).
+        tangent: fused reverse kernels take the radial gradient by forward tangent (snet_conv_bwd_fused_tangent); False:
+        the reverse-mode path (g_h2 / in-kernel tail -> g_emb -> snet_edge_embed_bwd), kept for A/B runs and as the tests' reference.
         modal: fidelity channel (name from config['_modal_map'] or index) of a multi-modal model; the
         one-hot inputs of its linears become constant biases, shift/scale rows are selected at load.
         """
@@ -344,8 +346,7 @@ class HipForceEngine:
             raise ValueError(f"fused_terms must be one of {sorted(codes)} (or the C-ABI code 1..4)")
         self.fused_terms = int(codes.get(fused_terms, fused_terms))
         self.fused_mode = {v: k for k, v in codes.items()}[self.fused_terms]
-        self.overlap = bool(overlap)
-        self.halo_split = True   # False: exchange, then the whole convolution (A/B measurements of the overlap)
+        self.overlap, self.halo_split = bool(overlap), True   # False: exchange, then the whole convolution (A/B measurements of the overlap)
         self._side = None  # second stream, created on first use
         self._acc_descs = {}  # id(descriptor array) -> its all-accumulating copy (the arrays live as long as the engine)
         self.events = None  # set to [] to collect (name, start, end) HIP events per kernel class
@@ -434,6 +435,7 @@ class HipForceEngine:
                 L.fused_fwd = L.fplan is not None and fused in ('auto', True, 'fwd')
                 L.fused_bwd = L.fplan is not None and fused in ('auto', True, 'bwd')
                 L.tile_mode = int(self.lib.snet_fused_plan_tile_mode(L.fplan)) if L.fplan is not None else 0
+                L.tangent = bool(L.fused_bwd and tangent and self.lib.snet_fused_plan_prefers_tangent(L.fplan))   # per shape, DESIGN 4j
                 # scalar-output layer (the last one): its source-row gradient as a forward convolution of the transposed
                 # product over the edges grouped by source -- gathers dout floats per edge instead of writing and
                 # re-reading a dx-float g_xe row (model_spec.transposed_scalar_conv)
@@ -697,18 +699,32 @@ class HipForceEngine:
         # (five launches of a latency-bound kernel at brick sizes; the rows are kept for the reverse pass anyway)
         h2_rows = g.n_pairs if pairs else E
         h2_of = {t_: self._new(h2_rows, 64) for t_, L_ in enumerate(self.layers) if L_.fused_fwd or L_.fused_bwd}
+        # layers whose reverse kernel runs in tangent mode also get h2' = d h2 / d|r| per row, from the same launch: the radial branch
+        # is a function of |r| alone, so dE/d|r_e| = sum_k g_w[e, k] (h2' W2)[k] needs no reverse pass through the radial MLP
+        h2d_of = {t_: self._new(h2_rows, 64) for t_, L_ in enumerate(self.layers) if L_.tangent}
         with _Span(self, 'radial_mlp_hidden_fwd'):
-            ts = sorted(h2_of)
-            for i in range(0, len(ts), 8):
-                grp = ts[i:i + 8]
-                plans = (C.c_void_p * len(grp))(*[self.layers[t_].mlp_plan for t_ in grp])
-                outs = (C.c_void_p * len(grp))(*[h2_of[t_].data_ptr() for t_ in grp])
-                _lib.check(lib.snet_radial_mlp_hidden_fwd_layers(plans, len(grp), _ptr(emb_p if pairs else emb), h2_rows, outs, st),
-                           'snet_radial_mlp_hidden_fwd_layers')
+            demb = None
+            if h2d_of:
+                demb = self._new(h2_rows, nb)
+                _lib.check(lib.snet_edge_embed_tangent(C.byref(self.edge_params), self.coeffs, _ptr(g.edge_vec),
+                                                       _ptr(g.pair_edge) if pairs else None, h2_rows, _ptr(demb), st), 'snet_edge_embed_tangent')
+            for tg_, ts in ((True, sorted(h2d_of)), (False, sorted(set(h2_of) - set(h2d_of)))):
+                for i in range(0, len(ts), 8):
+                    grp = ts[i:i + 8]
+                    plans = (C.c_void_p * len(grp))(*[self.layers[t_].mlp_plan for t_ in grp])
+                    outs = (C.c_void_p * len(grp))(*[h2_of[t_].data_ptr() for t_ in grp])
+                    if tg_:
+                        outs_d = (C.c_void_p * len(grp))(*[h2d_of[t_].data_ptr() for t_ in grp])
+                        _lib.check(lib.snet_radial_mlp_hidden_fwd_layers_tangent(plans, len(grp), _ptr(emb_p if pairs else emb), _ptr(demb),
+                                                                                 h2_rows, outs, outs_d, st),
+                                   'snet_radial_mlp_hidden_fwd_layers_tangent')
+                    else:
+                        _lib.check(lib.snet_radial_mlp_hidden_fwd_layers(plans, len(grp), _ptr(emb_p if pairs else emb), h2_rows, outs, st),
+                                   'snet_radial_mlp_hidden_fwd_layers')
         return SimpleNamespace(g=g, halo=halo, keep=keep, st=st, N=N, NT=NT, E=E, nb=nb, nsh=nsh, inter=inter, emb=emb, sh=sh, dsh=dsh,
                                pairs=pairs, w_row=w_row, emb_p=emb_p if pairs else None, side=side, w_ready=w_ready,
                                gw_bufs=gw_bufs if side is not None else None, gw_done=gw_done if side is not None else None,
-                               x=x, saved=saved, split=split, h2_of=h2_of)
+                               x=x, saved=saved, split=split, h2_of=h2_of, h2d_of=h2d_of)
 
     def _forward_layers(self, c):
         """the interaction layers (interaction_blocks.py:41-76): SI1, ghost exchange, self-connection, convolution, SI2, gate"""
@@ -872,7 +888,9 @@ class HipForceEngine:
         saved, split = c.saved, c.split
         sh_T = None   # spherical harmonics in source-grouped edge order (transposed scalar convolution)
         g_vec = torch.zeros(E, 3, dtype=torch.float32, device=self.dev)  # spherical part, all layers
-        g_emb = torch.zeros(E, nb, dtype=torch.float32, device=self.dev)
+        # layers in tangent mode put their radial gradient into g_vec themselves; g_emb exists for the others only
+        need_g_emb = any(not L_.tangent for L_ in self.layers)
+        g_emb = torch.zeros(E, nb, dtype=torch.float32, device=self.dev) if need_g_emb else None
         # fp16 operands of the fused reverse kernels: row maxima of the source rows and of the incoming gradient bound every
         # edge's g_w, from which the kernel derives that edge's power-of-two scale (no overflow possible).  The source-row
         # bounds of ALL layers come from one launch here (the rows have been complete since the forward pass).
@@ -940,13 +958,21 @@ class HipForceEngine:
                                    'snet_segment_sum_rows')
 
             if L.fused_bwd:
-                g_h2 = None if L.mlp_tail else self._new(E, 64)
+                tangent = L.tangent
+                g_h2 = None if (L.mlp_tail or tangent) else self._new(E, 64)
                 x_max = x_max_of.pop(t, None)   # (computed before the layer loop)
+                h2d = c.h2d_of.pop(t, None)
 
                 def bwd_tiles(tp_, tn_, nt_):
                     if nt_ <= 0:
                         return
                     with _Span(self, f'conv_bwd_fused[{ls.conv.tag}]'):
+                        if tangent:
+                            _lib.check(lib.snet_conv_bwd_fused_tangent(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(h2d), _ptr(w_row),
+                                                                       _ptr(g.row_ptr), _ptr(g.src), _ptr(tp_), _ptr(tn_), nt_, L.scale,
+                                                                       _ptr(g_m), _ptr(g_xe), _ptr(g.edge_vec), _ptr(g_vec), _ptr(x_max),
+                                                                       _ptr(g_max), st), 'snet_conv_bwd_fused_tangent')
+                            return
                         _lib.check(lib.snet_conv_bwd_fused(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(w_row),
                                                            _ptr(g.row_ptr), _ptr(g.src), _ptr(tp_), _ptr(tn_), nt_, L.scale,
                                                            _ptr(g_m), _ptr(g_xe), _ptr(g_h2),
@@ -991,7 +1017,7 @@ class HipForceEngine:
                         else:
                             halo.reverse(g_h, N)
             del g_xe
-            if L.fused_bwd and L.mlp_tail:
+            if L.fused_bwd and (L.mlp_tail or L.tangent):
                 pass
             elif L.fused_bwd:
                 with _Span(self, 'radial_mlp_hidden_bwd'):
@@ -1022,8 +1048,9 @@ class HipForceEngine:
             saved[t] = None
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-        _lib.check(lib.snet_edge_embed_bwd(C.byref(self.edge_params), self.coeffs, _ptr(g.edge_vec), E, _ptr(g_emb),
-                                           None, _ptr(g_vec), 1, st), 'snet_edge_embed_bwd')
+        if g_emb is not None:
+            _lib.check(lib.snet_edge_embed_bwd(C.byref(self.edge_params), self.coeffs, _ptr(g.edge_vec), E, _ptr(g_emb),
+                                               None, _ptr(g_vec), 1, st), 'snet_edge_embed_bwd')
         return g_vec
 
     def _forces(self, c, g_vec, e_atom, energy, want_atomic_virial: bool):

@@ -43,6 +43,7 @@ def shape_sources(spec: ConvSpec):
     srcs = [(f'conv_{spec.tag}.hip', codegen.gen_conv(spec))]
     if codegen_fused.fusable(spec):
         srcs.append((f'convf_{spec.tag}.hip', codegen_fused.gen_conv_fused(spec)))
+        srcs.append((f'convft_{spec.tag}.hip', codegen_fused.gen_conv_fused_tangent(spec)))
     return srcs
 
 
