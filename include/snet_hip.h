@@ -461,6 +461,39 @@ int snet_fire_step(double *pos, double *vel, const float *forces, const double *
                    int32_t *n_steps, double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max,
                    int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step, void *stream);
 
+/* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
+ * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
+ * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of
+ * forces (fp32 [n_atoms,3], as the engine returns them; forces_extra, fp64 [n_atoms,3] or NULL, is added to them in fp64) and of
+ * mass (fp64 [n_atoms], amu).  Per system on the device: sys_id (int32, the caller's index of the system: read by the noise
+ * stream only), kT (fp64, eV), step_index (int32, in/out), e_kin (fp64, out).  The step is BAOAB (Leimkuhler, Matthews 2013; the
+ * rule of TorchSim's nvt_langevin), folded around the force call so that one launch finishes step k and begins step k + 1.  With
+ * F the summed forces at the current positions, for every system:
+ *   if phase & 1 (FINISH):  v += (dt/2) ACC F / m
+ *   e_kin[s] = sum_i (1/2) m_i |v_i|^2 / ACC                       (always)
+ *   if phase & 2 (START):   v += (dt/2) ACC F / m
+ *                           c2 == 0:  x += dt v                                                          (NVE)
+ *                           else:     x += (dt/2) v;  v = c1 v + c2 sqrt(kT[s] ACC / m) xi;  x += (dt/2) v
+ *                           step_index[s] += 1
+ * c1 = exp(-gamma dt) and c2 = sqrt(1 - c1^2) are the caller's (computed once on the host in fp64).  phase 0 writes e_kin only.
+ * xi: three standard normals per atom from Philox4x32-10 (Random123 constants: multipliers 0xD2511F53, 0xCD9E8D57, key increments
+ * 0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and counter (a, sys_id[s], step_index[s], tag): a = the atom's
+ * index within its system, step_index[s] before the increment, tag 0 for this thermostat and 1 for snet_mdb_init_velocities.  The
+ * four output words w_k give u_k = (w_k + 0.5) 2^-32 and xi_x = sqrt(-2 ln u0) cos(2 pi u1), xi_y = sqrt(-2 ln u0) sin(2 pi u1),
+ * xi_z = sqrt(-2 ln u2) cos(2 pi u3).  An atom's noise depends on (seed, system id, atom, step) only: not on the batch, the slot
+ * or the launch grid.  With c2 == 0 no random number is generated.
+ * One 256-thread workgroup per system, fp64 sums in a fixed order, no atomics: two runs give identical bits, and a system's
+ * results do not depend on the other systems of the launch.
+ *
+ * snet_mdb_init_velocities: v_i = sqrt(kT[s] ACC / m_i) xi_i with the same generator (tag 1, step word 0).  remove_com != 0 and
+ * more than one atom: the centre-of-mass velocity sum m v / sum m is subtracted and the velocities are scaled so that the kinetic
+ * energy is (1/2) (3 n_s - 3) kT[s] exactly; remove_com != 0 and one atom: zero velocity.                                      */
+int snet_mdb_step(double *pos, double *vel, const float *forces, const double *forces_extra, const double *mass, int64_t n_atoms,
+                  const int32_t *seg_ptr, const int32_t *sys_id, int32_t n_sys, const double *kT, int32_t *step_index,
+                  double *e_kin, double dt, double c1, double c2, uint64_t seed, int32_t phase, void *stream);
+int snet_mdb_init_velocities(double *vel, const double *mass, int64_t n_atoms, const int32_t *seg_ptr, const int32_t *sys_id,
+                             int32_t n_sys, const double *kT, uint64_t seed, int32_t remove_com, void *stream);
+
 /* ---- whole-model sequencer ------------------------------------------------------------------
  * replaces, for a native (C++) host, `model.forward(input_dict)` + `torch::autograd::grad(...)` of
  * the LAMMPS pair styles (sevenn/pair_e3gnn/pair_e3gnn.cpp:200-207, pair_e3gnn_parallel.cpp:424-503)

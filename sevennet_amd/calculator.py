@@ -172,6 +172,22 @@ def load_reference_checkpoint(path: str, strict_reference: bool = False):
     return cfg, fix_old_convolution_signs(cfg, sd, strict_reference)
 
 
+def atoms_velocities(atoms_list, kw: dict) -> dict:
+    """the keyword arguments of md_many for ASE-like objects: `velocities` from get_velocities() when the caller passed none
+    and every object has some (an object without the method, or one that returns None, has none).  Objects of the ase package
+    itself are refused unless the caller passes `velocities` (ValueError): their unit is not A/fs."""
+    if kw.get('velocities') is not None:
+        return kw
+    for b, a in enumerate(atoms_list):   # ASE's velocity unit is A / (10.18 fs): read as A/fs it would be wrong tenfold, silently
+        if type(a).__module__.split('.')[0] == 'ase':
+            raise ValueError(f'system {b} is an ase object, whose velocities are in ASE units, not A/fs: pass velocities= in A/fs '
+                             '(get_velocities() * ase.units.fs) explicitly, and divide what is written back by ase.units.fs')
+    vels = [a.get_velocities() if hasattr(a, 'get_velocities') else None for a in atoms_list]
+    if any(v is None for v in vels):
+        return kw
+    return dict(kw, velocities=[np.asarray(v, np.float64) for v in vels])
+
+
 class SevenNetCalculator(Calculator):
     """Supporting properties: 'free_energy', 'energy', 'forces', 'stress', 'stresses', 'energies'."""
 
@@ -236,6 +252,7 @@ class SevenNetCalculator(Calculator):
         self.model = HipForceEngine(cfg, sd, device=str(self.device), modal=self.modal)
         self._z2type = np.full(120, -1, np.int64)  # sequential.py:80-83
         self.relax_info: Optional[Dict[str, int]] = None   # counters of the last relax_many call
+        self.md_info: Optional[Dict[str, int]] = None      # counters of the last md_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -324,6 +341,41 @@ class SevenNetCalculator(Calculator):
         results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
         for a, r in zip(atoms_list, results):
             a.set_positions(r['positions'])
+        return results
+
+    def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+        """`steps` steps of `dt` fs of NVE or Langevin MD for B structures at once (sevennet_amd.md.md_batch): positions,
+        velocities, energy logs and trajectory frames stay on the GPU from the first step to the last and come to the host
+        once.  masses_list in amu (the caller's: this package has no table of atomic masses).  kw: temperature (K, scalar
+        or per system), friction (1/fs; 0 = NVE), velocities (A/fs; None: drawn at `temperature`), seed, log_every,
+        traj_every, remove_com, system_ids, extra (as md_batch).  One dict per system, in the given order: the keys of `compute` (the last
+        engine call, at the returned positions) plus `positions`, `velocities`, `e_pot`, `e_kin`, `temperature` and, with
+        traj_every > 0, `trajectory`.  The call's counters are kept as `self.md_info`."""
+        from .md import md_batch
+        if not len(numbers_list) == len(positions_list) == len(masses_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '
+                             f'{len(masses_list)} mass arrays')
+        results, self.md_info = md_batch(self.model, self._types_list(numbers_list), list(positions_list), list(masses_list), cells,
+                                         pbcs, cutoff=self.cutoff, dt=dt, steps=steps,
+                                         want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+        """`md_many` over ASE-like objects (get_atomic_numbers / get_positions / get_masses / get_cell / get_pbc, and
+        get_velocities where the object has velocities): positions and velocities are written back with `set_positions` /
+        `set_velocities`.  Velocities at this surface are in A/fs, read and written as they are.  ASE's own time unit is
+        A sqrt(amu / eV) = 10.1805 fs, so the velocities of a real ase.Atoms are in A / (10.1805 fs): multiply
+        get_velocities() by ase.units.fs (0.0982269) on the way in and divide by it on the way out, or pass
+        `velocities=` in A/fs yourself (it takes precedence over the objects').  Because the mistake would be silent, objects of
+        the ase package are refused (ValueError) unless `velocities=` is passed."""
+        from .d3 import _atoms_args
+        atoms_list = list(atoms_list)
+        numbers, positions, cells, pbcs = _atoms_args(atoms_list)
+        results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
+                               **atoms_velocities(atoms_list, kw))
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
+            a.set_velocities(r['velocities'])
         return results
 
     def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:

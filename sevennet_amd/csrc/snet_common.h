@@ -179,6 +179,21 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// sums of NV per-thread values over a 256-thread workgroup, in a fixed order: xor tree inside a wave, then waves 0..3 in
+// sequence.  Every thread returns the same bits.  `sm` is reused by the next call: the trailing barrier protects it.
+// (the one-workgroup-per-system kernels: snet_relax.hip, snet_mdstep.hip)
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double (*sm)[4]) {
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    const double t = wave_sum_d(v[c]);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][c] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < NV; ++c) v[c] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
+  __syncthreads();
+}
 
 // ---- cross-lane exchange at VALU speed (no LDS): gfx950 permlane swaps + DPP -------------------
 // a + b where the "low" lanes (bit 5 / bit 4 of the lane id clear) end up with a_self + a_partner

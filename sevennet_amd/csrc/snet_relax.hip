@@ -27,20 +27,7 @@ __device__ __forceinline__ double wave_max_d(double v) {
   return v;
 }
 
-// sums of NV per-thread values over the workgroup, in a fixed order: xor tree inside a wave, then waves 0..3 in sequence.
-// Every thread returns the same bits.  `sm` is reused by the next call: the trailing barrier protects it.
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*sm)[4]) {
-#pragma unroll
-  for (int c = 0; c < NV; ++c) {
-    const double t = snet::wave_sum_d(v[c]);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][c] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < NV; ++c) v[c] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
-  __syncthreads();
-}
+using snet::block_sum;   // per-system sums in a fixed order (snet_common.h)
 
 __device__ __forceinline__ void load_force(const float *__restrict__ f, const double *__restrict__ fx, int64_t i, double (&F)[3]) {
 #pragma unroll

@@ -242,6 +242,7 @@ class SevenNetD3Calculator(_SumBase):
         else:
             self.calcs = list(pair)
         self.relax_info = None   # counters of the last relax_many call
+        self.md_info = None      # counters of the last md_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -304,4 +305,41 @@ class SevenNetD3Calculator(_SumBase):
         results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
         for a, r in zip(atoms_list, results):
             a.set_positions(r['positions'])
+        return results
+
+    def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.md_many` on the sum of the model's and the D3 forces (sevennet_amd.md): one dict per system
+        with the summed keys of `compute` at the returned positions plus `positions`, `velocities`, `e_pot` (D3 energy
+        included), `e_kin`, `temperature` (and `trajectory`); the counters are kept as `self.md_info`.  As in `relax_many`,
+        the D3 batch is prepared on the host: this path copies the positions down and the D3 forces up once per step."""
+        import torch
+        snet, d3 = self.calcs
+        numbers_list, positions_list = list(numbers_list), list(positions_list)
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        numbers = prepare_d3_batch(numbers_list, positions_list, cells, pbcs, d3.rthr, d3.cnthr).numbers   # Z range, cells
+        last_d3: List[Dict[str, Any]] = []
+
+        def d3_forces(pos_dev, seg_ptr_host, slots):
+            last_d3[:] = d3.engine.compute_many(numbers, pos_dev.cpu().numpy(), cells, pbcs, n_atoms=np.diff(seg_ptr_host))
+            dev = pos_dev.device
+            return (torch.as_tensor(np.concatenate([r['forces'] for r in last_d3])).to(dev),
+                    torch.as_tensor(np.array([r['energy'] for r in last_d3])).to(dev))
+
+        results = snet.md_many(numbers_list, positions_list, masses_list, cells, pbcs, dt, steps, extra=d3_forces, **kw)
+        self.md_info = snet.md_info
+        # the model's results and the D3 results of the last step's evaluations, both at the returned positions
+        return [self._sum(a, D3Calculator._results(b)) for a, b in zip(results, last_d3)]
+
+    def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+        """`md_many` over ASE-like objects, as SevenNetCalculator.md_many_atoms (velocities in A/fs, see there): positions
+        and velocities are written back with `set_positions` / `set_velocities`"""
+        from .calculator import atoms_velocities
+        atoms_list = list(atoms_list)
+        numbers, positions, cells, pbcs = _atoms_args(atoms_list)
+        results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
+                               **atoms_velocities(atoms_list, kw))
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
+            a.set_velocities(r['velocities'])
         return results

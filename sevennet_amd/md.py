@@ -1,0 +1,263 @@
+"""Batched NVE / Langevin molecular dynamics at fixed cells, the state on the device from the first step to the last.
+
+`md_batch` integrates B structures at once: per step one batched neighbor build (sevennet_amd.batch), one engine call and one
+`snet_mdb_step` launch (csrc/snet_mdstep.hip: one workgroup per system, fp64, fixed summation order).  Positions, velocities,
+the per-system step counters, the energy logs and the trajectory frames are device tensors; the integrator reads nothing back
+while it runs, and everything comes to the host once, after the loop.  What still synchronises per step is the batched
+neighbor build, which reads the edge total to size its arrays (a skinned list kept over several steps would remove it; that is
+not done here).
+
+The integrator is BAOAB (Leimkuhler, Matthews, Appl. Math. Res. Express 2013, 34; TorchSim's `nvt_langevin` states the same
+rule), folded around the force call so that one launch finishes step k and begins step k + 1; with friction 0 it is velocity
+Verlet.  The noise is Philox4x32-10 counted by (atom within its system, system id, step): a system's trajectory does not
+depend on the batch it runs in.  The rule is written out in include/snet_hip.h (snet_mdb_step) and restated in fp64 numpy in
+tests/md_ref.py.  Units: eV, A, fs, amu, K."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Any, Callable, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .batch import _as_host, batch_results, build_batch_graph
+from .relax import validate_relax_inputs
+
+ACC = 9.648533212e-3    # eV / (A amu) in A / fs^2
+KB = 8.617333262e-5     # eV / K
+FINISH, START = 1, 2    # snet_mdb_step phase bits
+
+
+def langevin_coefficients(friction: float, dt: float) -> Tuple[float, float]:
+    """(c1, c2) = (exp(-gamma dt), sqrt(1 - c1^2)) in fp64 on the host: what snet_mdb_step is given (friction 0: (1, 0), NVE)"""
+    c1 = math.exp(-float(friction) * float(dt))
+    return c1, math.sqrt(1.0 - c1 * c1)
+
+
+def _system_of(a_ptr: np.ndarray, row: int) -> int:
+    return int(np.searchsorted(a_ptr, row, side='right')) - 1
+
+
+def _per_atom(x, n_at: np.ndarray, width: int, what: str) -> np.ndarray:
+    """per-system sequences or one flat array -> fp64 [N] (width 0) or [N, width]; ValueError names the system"""
+    N = int(n_at.sum())
+    shape = (N,) if width == 0 else (N, width)
+    if isinstance(x, (list, tuple)) and len(x) and not np.isscalar(x[0]) and not (isinstance(x[0], torch.Tensor) and x[0].ndim == 0):
+        if len(x) != len(n_at):
+            raise ValueError(f'{len(n_at)} systems but {len(x)} {what} arrays')
+        parts = []
+        for b, p in enumerate(x):
+            p = _as_host(p, np.float64)
+            want = (int(n_at[b]),) if width == 0 else (int(n_at[b]), width)
+            if p.shape != want:
+                raise ValueError(f'system {b}: {what} of shape {p.shape}, {want} expected ({int(n_at[b])} atoms)')
+            parts.append(p)
+        return np.concatenate(parts)
+    x = _as_host(x, np.float64)
+    if x.shape != shape:
+        raise ValueError(f'{what} of shape {x.shape}: per-system arrays, or one flat array of shape {shape}, expected')
+    return x.copy()
+
+
+def validate_md_inputs(masses, n_at: np.ndarray, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
+                       system_ids=None):
+    """Host checks of everything md_batch takes beyond the relax inputs -> (mass fp64 [N], velocities fp64 [N,3] or None, kT
+    fp64 [B] in eV, system ids int32 [B]).  ValueError names the system."""
+    B = len(n_at)
+    a_ptr = np.concatenate([[0], np.cumsum(n_at)])
+    if not (isinstance(dt, (int, float, np.floating, np.integer)) and dt > 0 and math.isfinite(dt)):
+        raise ValueError(f'dt = {dt}: a positive time step (fs) is required')
+    for name, v, low in (('steps', steps, 0), ('log_every', log_every, 1), ('traj_every', traj_every, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < low:
+            raise ValueError(f'{name} = {v}: an integer >= {low} is required')
+    real = (int, float, np.floating, np.integer)
+    if isinstance(friction, bool) or not isinstance(friction, real) or not (friction >= 0 and math.isfinite(friction)):
+        raise ValueError(f'friction = {friction!r}: a friction (1/fs) >= 0 is required')
+    if friction > 0 and langevin_coefficients(friction, dt)[1] == 0.0:   # exp(-gamma dt) rounds to 1: the kernel would run NVE
+        raise ValueError(f'friction = {friction} with dt = {dt}: friction * dt is below fp64 resolution, the thermostat would '
+                         'do nothing (pass friction = 0 for NVE)')
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f'seed = {seed!r}: an integer in [0, 2^64) is required')
+    if temperature is None:
+        if velocities is None:
+            raise ValueError('neither velocities nor temperature given: pass start velocities, or a temperature to draw them at')
+        if friction > 0:
+            raise ValueError(f'friction = {friction} needs a temperature: the thermostat has nothing to aim at')
+        kT = np.zeros(B)
+    else:
+        T = _as_host(temperature, np.float64)
+        if T.ndim == 0:
+            T = np.full(B, float(T))
+        if T.shape != (B,):
+            raise ValueError(f'temperature of shape {T.shape}: a scalar or one value per system ({B}) is required')
+        bad = ~((T >= 0) & np.isfinite(T))
+        if bad.any():
+            b = int(np.nonzero(bad)[0][0])
+            raise ValueError(f'system {b}: temperature = {T[b]} K, a finite temperature >= 0 is required')
+        kT = KB * T
+    mass = _per_atom(masses, n_at, 0, 'masses')   # (as many as atoms)
+    bad = ~((mass > 0) & np.isfinite(mass))
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {_system_of(a_ptr, i)}: mass = {mass[i]} amu, finite masses > 0 are required')
+    vel = None
+    if velocities is not None:
+        vel = _per_atom(velocities, n_at, 3, 'velocities')
+        fin = np.isfinite(vel).all(1)
+        if not fin.all():
+            raise ValueError(f'system {_system_of(a_ptr, int(np.nonzero(~fin)[0][0]))}: non-finite velocity')
+    if system_ids is None:
+        ids = np.arange(B, dtype=np.int64)
+    else:
+        ids = _as_host(system_ids, np.int64).reshape(-1)
+        if len(ids) != B or (ids < 0).any() or (ids >= 2 ** 31).any():
+            raise ValueError(f'system_ids: {B} integers in [0, 2^31) are required')
+    return mass, vel, kT, ids.astype(np.int32)
+
+
+def _check_tensors(name: str, ref: torch.Tensor, want) -> None:
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != ref.device or not t.is_cuda:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of shape {shape} on {ref.device} is required, got '
+                             f'{t.dtype} {tuple(t.shape)} on {t.device}')
+
+
+_P = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+
+
+def md_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor,
+            sys_id: torch.Tensor, kT: torch.Tensor, step_index: torch.Tensor, e_kin: torch.Tensor, dt: float, c1: float, c2: float,
+            seed: int, phase: int, forces_extra: Optional[torch.Tensor] = None) -> None:
+    """one `snet_mdb_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C ABI:
+    pos / vel / mass / kT / e_kin fp64, forces fp32, forces_extra fp64, seg_ptr / sys_id / step_index int32)"""
+    N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
+    want = [(pos, torch.float64, (N, 3)), (vel, torch.float64, (N, 3)), (forces, torch.float32, (N, 3)), (mass, torch.float64, (N,)),
+            (seg_ptr, torch.int32, (B + 1,)), (sys_id, torch.int32, (B,)), (kT, torch.float64, (B,)), (step_index, torch.int32, (B,)),
+            (e_kin, torch.float64, (B,))]
+    if forces_extra is not None:
+        want.append((forces_extra, torch.float64, (N, 3)))
+    _check_tensors('md_step', pos, want)
+    with torch.cuda.device(pos.device):
+        _lib.check(_lib.load().snet_mdb_step(
+            _P(pos), _P(vel), _P(forces), _P(forces_extra), _P(mass), N, _P(seg_ptr), _P(sys_id), B, _P(kT), _P(step_index), _P(e_kin),
+            float(dt), float(c1), float(c2), int(seed), int(phase), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            'snet_mdb_step')
+
+
+def init_velocities(vel: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor, sys_id: torch.Tensor, kT: torch.Tensor,
+                    seed: int, remove_com: bool = True) -> None:
+    """one `snet_mdb_init_velocities` launch on the current stream: Maxwell-Boltzmann velocities at kT (eV) into vel"""
+    N, B = int(vel.shape[0]), int(seg_ptr.numel()) - 1
+    _check_tensors('init_velocities', vel, [(vel, torch.float64, (N, 3)), (mass, torch.float64, (N,)), (seg_ptr, torch.int32, (B + 1,)),
+                                            (sys_id, torch.int32, (B,)), (kT, torch.float64, (B,))])
+    with torch.cuda.device(vel.device):
+        _lib.check(_lib.load().snet_mdb_init_velocities(
+            _P(vel), _P(mass), N, _P(seg_ptr), _P(sys_id), B, _P(kT), int(seed), int(bool(remove_com)),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'snet_mdb_init_velocities')
+
+
+def md_loop(engine, types: np.ndarray, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray,
+            n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, *, cutoff: float, dt: float, steps: int, friction: float,
+            seed: int, log_every: int, traj_every: int, remove_com: bool, extra: Optional[Callable], want_atomic_virial: bool):
+    """The MD loop on validated inputs (`validate_relax_inputs`, `validate_md_inputs`) -> (graph and engine output of the last
+    force call, dict of device tensors: pos, vel [N,3], e_pot, e_kin [samples,B], traj [frames,N,3] or None, step_index [B]; info)"""
+    dev = engine.dev
+    ns = engine.spec.num_species
+    B, steps, log_every, traj_every = len(n_atoms), int(steps), int(log_every), int(traj_every)
+    sp_host = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+    slots = np.arange(B)
+    c1, c2 = langevin_coefficients(friction, dt)
+    up = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a, dtype)).to(dev)  # noqa: E731
+    with torch.cuda.device(dev):
+        pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
+               else up(positions, np.float64)).reshape(-1, 3).clone()
+        N = int(pos.shape[0])
+        ty, m_d, kT_d, id_d, seg = up(types, np.int32), up(mass, np.float64), up(kT, np.float64), up(ids, np.int32), up(sp_host, np.int32)
+        if vel0 is None:
+            vel = torch.empty_like(pos)
+            init_velocities(vel, m_d, seg, id_d, kT_d, seed, remove_com)
+        else:
+            vel = up(vel0, np.float64)
+        step_index = torch.zeros(B, dtype=torch.int32, device=dev)
+        e_kin = torch.zeros(B, dtype=torch.float64, device=dev)
+        e_pot_log = torch.zeros(steps // log_every + 1, B, dtype=torch.float64, device=dev)
+        e_kin_log = torch.zeros_like(e_pot_log)
+        traj = torch.zeros(steps // traj_every + 1, N, 3, dtype=torch.float64, device=dev) if traj_every > 0 else None
+        info = dict(n_force_calls=0, md_launches=0, system_steps_evaluated=0)
+        g = out = None
+        for k in range(steps + 1):
+            last = k == steps
+            g = build_batch_graph(ty, pos, cells, pbcs, cutoff, ns, n_atoms=n_atoms, device=dev, species_rows=engine.needs_species_rows)
+            out = engine.compute(g, want_atomic_virial=want_atomic_virial and last)
+            fx = ex = None
+            if extra is not None:
+                fx = extra(pos, sp_host, slots)
+                if isinstance(fx, tuple):
+                    fx, ex = fx
+                    ex = torch.as_tensor(ex).to(dev, torch.float64).reshape(B)
+                fx = torch.as_tensor(fx).to(dev, torch.float64).contiguous()
+            if traj is not None and k % traj_every == 0:
+                traj[k // traj_every].copy_(pos)   # x_k: the launch below moves on to x_{k+1}
+            md_step(pos, vel, out['forces'], m_d, seg, id_d, kT_d, step_index, e_kin, dt, c1, c2, seed,
+                    (FINISH if k > 0 else 0) | (0 if last else START), fx)
+            if k % log_every == 0:   # e_kin is the kinetic energy of v_k, the potential energy that of x_k
+                j = k // log_every
+                e_pot_log[j].copy_(out['energy_per_system'] if ex is None else out['energy_per_system'] + ex)
+                e_kin_log[j].copy_(e_kin)
+            info['n_force_calls'] += 1
+            info['md_launches'] += 1
+            info['system_steps_evaluated'] += B
+    return g, out, dict(pos=pos, vel=vel, e_pot=e_pot_log, e_kin=e_kin_log, traj=traj, step_index=step_index), info
+
+
+def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms) -> List[Dict[str, Any]]:
+    """`positions`, `velocities`, `e_pot`, `e_kin`, `temperature` (and `trajectory`) into each system's results dict: the one
+    transfer to the host"""
+    pos_h, vel_h = state['pos'].cpu().numpy(), state['vel'].cpu().numpy()
+    e_pot, e_kin = state['e_pot'].cpu().numpy(), state['e_kin'].cpu().numpy()
+    traj = None if state['traj'] is None else state['traj'].cpu().numpy()
+    for b, res in enumerate(results):
+        a0, a1 = int(seg_ptr_host[b]), int(seg_ptr_host[b + 1])
+        res['positions'], res['velocities'] = pos_h[a0:a1].copy(), vel_h[a0:a1].copy()
+        res['e_pot'], res['e_kin'] = e_pot[:, b].copy(), e_kin[:, b].copy()
+        res['temperature'] = 2.0 * res['e_kin'] / (3.0 * int(n_atoms[b]) * KB)
+        if traj is not None:
+            res['trajectory'] = traj[:, a0:a1].copy()
+    return results
+
+
+def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt: float, steps: int, temperature=None,
+             friction: float = 0.0, velocities=None, seed: int = 0, log_every: int = 1, traj_every: int = 0, remove_com: bool = True,
+             extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
+             system_ids=None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+    """`steps` MD steps of `dt` fs for B structures at fixed cells: NVE (friction 0) or Langevin at `temperature`.
+
+    engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `relax_batch`; masses (amu)
+    and velocities (A/fs) per system or flat like the positions; the caller's arrays are not modified.  temperature (K): a
+    scalar or one value per system; friction: gamma in 1/fs (> 0 needs a temperature).  velocities None: drawn at
+    `temperature` on the device (`remove_com`: each system's centre of mass at rest, kinetic energy (3 n - 3) kT / 2
+    exactly).  seed: of the noise (thermostat and draw); two runs with one seed give identical bits.  system_ids: the id each
+    system's noise is counted under, default 0..B-1 -- a system run alone under the id it had in a batch sees the same noise.
+    extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [B+1] on the host, ids int64 [B]: the index of
+    each system in this call) -> fp64 forces [N,3], or (forces, energy_per_system fp64 [B]), added to the model's each step
+    (the energies go into the potential-energy log).
+
+    Schedule: F0 = f(x0), one launch that starts step 1; then per step Fk = f(xk) and one launch that finishes step k and
+    starts step k + 1 (the last one only finishes).  steps = 0: one force call, one launch that moves nothing.
+
+    Returns (results, info).  results[b]: the dict of SevenNetCalculator.compute_many from the LAST engine call, which is at
+    the returned positions, plus `positions` and `velocities` [n,3] fp64, `e_pot`, `e_kin` (eV) and `temperature`
+    (2 e_kin / (3 n KB), K) over the logged steps -- sample j belongs to step j log_every -- and `trajectory` [frames,n,3]
+    (step j traj_every) when traj_every > 0.  info: n_force_calls == md_launches == steps + 1, system_steps_evaluated ==
+    B (steps + 1).  Invalid input raises ValueError before any device work."""
+    types, positions, n_at, cells, pbcs = validate_relax_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
+                                                                n_atoms=n_atoms)
+    mass, vel0, kT, ids = validate_md_inputs(masses, n_at, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
+                                             system_ids)
+    g, out, state, info = md_loop(engine, types, positions, mass, vel0, kT, ids, n_at, cells, pbcs, cutoff=cutoff, dt=dt, steps=steps,
+                                  friction=friction, seed=seed, log_every=log_every, traj_every=traj_every, remove_com=remove_com,
+                                  extra=extra, want_atomic_virial=want_atomic_virial)
+    results = batch_results(g, out, cells, want_atomic_virial)
+    return attach_md(results, state, g.seg_ptr_host, n_at), info
