@@ -241,6 +241,25 @@ def check(rc: int, what: str = ''):
         raise RuntimeError(f'{what} failed (rc={rc}): {msg.decode() if msg else "?"}')
 
 
+def ptr(t):
+    """a tensor's data pointer as a C-ABI argument (None: NULL)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream():
+    """the current torch stream as a C-ABI argument"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def check_device_tensors(name: str, ref, want) -> None:
+    """every (tensor, dtype, shape) of `want` is contiguous, of that dtype and shape, and on the GPU of `ref` (ValueError)"""
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != ref.device or not t.is_cuda:
+            raise ValueError(f'{name}: a contiguous {dtype} tensor of shape {shape} on {ref.device} is required, got '
+                             f'{t.dtype} {tuple(t.shape)} on {t.device}')
+
+
 def compiled_conv_tags():
     lib = load()
     return [lib.snet_conv_shape_tag(i).decode() for i in range(lib.snet_conv_num_shapes())]

@@ -1,0 +1,82 @@
+"""The ASE-facing side of the calculators, once: the `Calculator` base (ASE's, or a stand-in where ASE is absent), the
+arguments of the batched surfaces read from ASE-like objects, and the `*_atoms` adapters over them."""
+from __future__ import annotations
+
+from typing import Any, Dict, List
+
+import numpy as np
+
+try:  # ASE is optional: without it the calculators are plain objects that expose compute() and the batched surfaces
+    from ase.calculators.calculator import Calculator, all_changes
+    HAVE_ASE = True
+except ImportError:  # pragma: no cover - depends on the environment
+    HAVE_ASE = False
+    all_changes = ['positions', 'numbers', 'cell', 'pbc']
+
+    class Calculator:  # minimal stand-in with the attributes the calculators use
+        def __init__(self, **kwargs):
+            self.results: Dict[str, Any] = {}
+            self.atoms = None
+
+        def calculate(self, atoms=None, properties=None, system_changes=None):
+            self.atoms = atoms
+
+
+def atoms_args(atoms_list):
+    """(numbers_list, positions_list, cells[B,3,3], pbcs[B,3]) of ASE-like objects (get_atomic_numbers / get_positions /
+    get_cell / get_pbc)"""
+    atoms_list = list(atoms_list)
+    return ([a.get_atomic_numbers() for a in atoms_list], [a.get_positions() for a in atoms_list],
+            np.array([np.array(a.get_cell(), np.float64).reshape(3, 3) for a in atoms_list]).reshape(-1, 3, 3),
+            np.array([np.asarray(a.get_pbc(), bool).reshape(3) for a in atoms_list]).reshape(-1, 3))
+
+
+def atoms_velocities(atoms_list, kw: dict) -> dict:
+    """the keyword arguments of md_many for ASE-like objects: `velocities` from get_velocities() when the caller passed none
+    and every object has some (an object without the method, or one that returns None, has none).  Objects of the ase package
+    itself are refused unless the caller passes `velocities` (ValueError): their unit is not A/fs."""
+    if kw.get('velocities') is not None:
+        return kw
+    for b, a in enumerate(atoms_list):   # ASE's velocity unit is A / (10.18 fs): read as A/fs it would be wrong tenfold, silently
+        if type(a).__module__.split('.')[0] == 'ase':
+            raise ValueError(f'system {b} is an ase object, whose velocities are in ASE units, not A/fs: pass velocities= in A/fs '
+                             '(get_velocities() * ase.units.fs) explicitly, and divide what is written back by ase.units.fs')
+    vels = [a.get_velocities() if hasattr(a, 'get_velocities') else None for a in atoms_list]
+    if any(v is None for v in vels):
+        return kw
+    return dict(kw, velocities=[np.asarray(v, np.float64) for v in vels])
+
+
+class ManyAtomsMixin:
+    """`calculate_many`, `relax_many_atoms` and `md_many_atoms` over ASE-like objects, for a class that has `compute_many`,
+    `relax_many` and `md_many` (a class without the latter two inherits adapters that fail where they are called)"""
+
+    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
+        """`compute_many` over ASE-like objects (anything with get_atomic_numbers / get_positions / get_cell / get_pbc)"""
+        return self.compute_many(*atoms_args(atoms_list))
+
+    def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """`relax_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc / set_positions): the
+        relaxed positions are written back with `set_positions`"""
+        atoms_list = list(atoms_list)
+        results = self.relax_many(*atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
+        return results
+
+    def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+        """`md_many` over ASE-like objects (get_atomic_numbers / get_positions / get_masses / get_cell / get_pbc, and
+        get_velocities where the object has velocities): positions and velocities are written back with `set_positions` /
+        `set_velocities`.  Velocities at this surface are in A/fs, read and written as they are.  ASE's own time unit is
+        A sqrt(amu / eV) = 10.1805 fs, so the velocities of a real ase.Atoms are in A / (10.1805 fs): multiply
+        get_velocities() by ase.units.fs (0.0982269) on the way in and divide by it on the way out, or pass
+        `velocities=` in A/fs yourself (it takes precedence over the objects').  Because the mistake would be silent, objects of
+        the ase package are refused (ValueError) unless `velocities=` is passed."""
+        atoms_list = list(atoms_list)
+        numbers, positions, cells, pbcs = atoms_args(atoms_list)
+        results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
+                               **atoms_velocities(atoms_list, kw))
+        for a, r in zip(atoms_list, results):
+            a.set_positions(r['positions'])
+            a.set_velocities(r['velocities'])
+        return results

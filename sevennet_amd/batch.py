@@ -12,8 +12,7 @@ what `SevenNetCalculator.compute` does for them -- and `concat_graphs` splices t
 """
 from __future__ import annotations
 
-import ctypes as C
-from typing import List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -104,14 +103,40 @@ def _normalize(types, positions, cells, pbcs, n_atoms):
     return types, positions, n_atoms, cells, np.ascontiguousarray(pbcs.reshape(B, 3))
 
 
+def system_of(a_ptr, row: int) -> int:
+    """the system that owns flat row `row`, for a_ptr[B+1] = where each system's rows start"""
+    return int(np.searchsorted(a_ptr, row, side='right')) - 1
+
+
+def validate_batch_inputs(types, positions, cells, pbcs, cutoff: float, num_species: int, n_atoms=None,
+                          max_atoms: int = BATCH_MAX_ATOMS):
+    """Everything `build_batch_graph` would reject, found on the host before the first launch: -> (types int64 [N] on the
+    host, positions [N,3] (host array or the caller's tensor), n_atoms [B], cells [B,3,3], pbcs [B,3]).  ValueError names the
+    system."""
+    types, positions, n_at, cells, pbcs = _normalize(types, positions, cells, pbcs, n_atoms)
+    types = _as_host(types, np.int64).reshape(-1)
+    a_ptr = np.concatenate([[0], np.cumsum(n_at)])
+    bad = (types < 0) | (types >= num_species)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {system_of(a_ptr, i)}: unknown species index {int(types[i])} (the model has {num_species})')
+    if not isinstance(positions, torch.Tensor):   # (device tensors are not read back for this)
+        fin = np.isfinite(positions).all(1)
+        if not fin.all():
+            raise ValueError(f'system {system_of(a_ptr, int(np.nonzero(~fin)[0][0]))}: non-finite position')
+    if not cutoff > 0:
+        raise ValueError(f'cutoff = {cutoff}: a positive cutoff is required')
+    classify_systems(n_at, cells, pbcs, cutoff, max_atoms)   # singular cells
+    return types, positions, n_at, cells, pbcs
+
+
 def _batched_neighbors(pos: torch.Tensor, atom_ptr: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, cutoff: float, dev,
                        with_shifts: bool, extra_check: Optional[torch.Tensor] = None):
     """(row_ptr, src, center, edge_vec, shifts) of the systems [atom_ptr[b], atom_ptr[b+1]) of pos (device fp64): one count
     launch, one scan, one fill launch and one device->host sync (the edge total; `extra_check`, a device flag, rides along)"""
     lib = _lib.load()
     n, B = int(pos.shape[0]), len(atom_ptr) - 1
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    st, P = _lib.stream(), _lib.ptr
     ap = torch.as_tensor(atom_ptr.astype(np.int32)).to(dev)
     cd = torch.as_tensor(np.ascontiguousarray(cells.reshape(B, 9))).to(dev)
     pd = torch.as_tensor(pbcs.astype(np.int32)).to(dev)
@@ -134,7 +159,7 @@ def _batched_neighbors(pos: torch.Tensor, atom_ptr: np.ndarray, cells: np.ndarra
     shifts = torch.empty(E, 3, dtype=torch.int32, device=dev) if with_shifts else None
     if E:
         _lib.check(lib.snet_batch_nl_fill(P(pos), P(ap), B, P(cd), P(pd), n, float(cutoff), P(row_ptr), P(src), P(center), P(ev),
-                                          None if shifts is None else P(shifts), st), 'snet_batch_nl_fill')
+                                          P(shifts), st), 'snet_batch_nl_fill')
     return row_ptr, src, center, ev, shifts, E
 
 
@@ -261,6 +286,48 @@ def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species:
             a0, a1 = int(a_ptr[b]), int(a_ptr[b + 1])
             pieces[b] = _fallback_graph(ty[a0:a1], pos[a0:a1], cells[b], pbcs[b], cutoff, dev, with_shifts)
         return concat_graphs(pieces, num_species if species_rows else 0, share_pairs)
+
+
+class BatchForces:
+    """The force call of a batched driver (relax.fire_loop, md.md_loop): one `build_batch_graph`, one engine call and one call
+    of `extra` per evaluation, and the counters of all of them.
+
+    engine: a HipForceEngine; types int64 [N] on the host, n_atoms [B], cells [B,3,3], pbcs [B,3] as `validate_batch_inputs`
+    returns them.  extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [b+1] on the host, ids int64
+    [b]: the caller's index of each system of the current batch) -> forces [N,3], or (forces, energy_per_system [b]); numpy or
+    torch, on any device.  Nothing touches the device before the first evaluation."""
+
+    def __init__(self, engine, types: np.ndarray, n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, cutoff: float,
+                 extra: Optional[Callable] = None):
+        self.engine, self.types, self.n_atoms, self.cells, self.pbcs = engine, types, np.asarray(n_atoms, np.int64), cells, pbcs
+        self.cutoff, self.extra = cutoff, extra
+        self.a_ptr = np.concatenate([[0], np.cumsum(self.n_atoms)])
+        self.n_force_calls = 0            # engine calls
+        self.system_steps_evaluated = 0   # systems in the batch, summed over the engine calls
+        self._ids = self._ty = None       # the systems whose species indices are on the device, and those indices
+
+    def __call__(self, pos: torch.Tensor, ids=None, want_atomic_virial: bool = False, with_extra: bool = True):
+        """Evaluate the systems `ids` (default: all, in the caller's order) at their flat device positions `pos` -> (graph,
+        the engine's output, extra forces fp64 [N,3] contiguous on the device or None, extra energies fp64 [b] or None)"""
+        eng = self.engine
+        dev = eng.dev
+        ids = np.arange(len(self.n_atoms)) if ids is None else np.asarray(ids, np.int64)
+        if self._ids is None or not np.array_equal(ids, self._ids):   # first call, or the batch has been repacked
+            rows = np.concatenate([np.arange(self.a_ptr[b], self.a_ptr[b + 1]) for b in ids])
+            self._ids, self._ty = ids.copy(), torch.as_tensor(self.types[rows].astype(np.int32)).to(dev)
+        g = build_batch_graph(self._ty, pos, self.cells[ids], self.pbcs[ids], self.cutoff, eng.spec.num_species,
+                              n_atoms=self.n_atoms[ids], device=dev, species_rows=eng.needs_species_rows)
+        out = eng.compute(g, want_atomic_virial=want_atomic_virial)
+        self.n_force_calls += 1
+        self.system_steps_evaluated += len(ids)
+        fx = ex = None
+        if self.extra is not None and with_extra:
+            fx = self.extra(pos, g.seg_ptr_host, ids)
+            if isinstance(fx, tuple):
+                fx, ex = fx
+                ex = torch.as_tensor(ex).to(dev, torch.float64).reshape(len(ids))
+            fx = torch.as_tensor(fx).to(dev, torch.float64).contiguous()
+        return g, out, fx, ex
 
 
 def batch_results(g: Graph, out: dict, cells, with_atomic_virial: bool = False) -> List[dict]:

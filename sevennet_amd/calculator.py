@@ -23,25 +23,10 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 import torch
 
+from .atoms import Calculator, ManyAtomsMixin, all_changes
 from .engine import HipForceEngine, build_graph
 from .neighbor import neighbor_list
 from .neighbor_gpu import build_graph_gpu, gpu_neighbor_supported
-
-try:  # ASE is not a hard dependency of the engine
-    from ase.calculators.calculator import Calculator, all_changes
-    _HAVE_ASE = True
-except ImportError:  # pragma: no cover - depends on the environment
-    _HAVE_ASE = False
-    all_changes = ['positions', 'numbers', 'cell', 'pbc']
-
-    class Calculator:  # minimal stand-in so the class below is importable without ASE
-        def __init__(self, **kwargs):
-            self.results: Dict[str, Any] = {}
-            self.atoms = None
-
-        def calculate(self, atoms=None, properties=None, system_changes=None):
-            self.atoms = atoms
-
 
 _OLD_MODULE_NAMES = {
     'EdgeEmbedding': 'edge_embedding',
@@ -172,23 +157,7 @@ def load_reference_checkpoint(path: str, strict_reference: bool = False):
     return cfg, fix_old_convolution_signs(cfg, sd, strict_reference)
 
 
-def atoms_velocities(atoms_list, kw: dict) -> dict:
-    """the keyword arguments of md_many for ASE-like objects: `velocities` from get_velocities() when the caller passed none
-    and every object has some (an object without the method, or one that returns None, has none).  Objects of the ase package
-    itself are refused unless the caller passes `velocities` (ValueError): their unit is not A/fs."""
-    if kw.get('velocities') is not None:
-        return kw
-    for b, a in enumerate(atoms_list):   # ASE's velocity unit is A / (10.18 fs): read as A/fs it would be wrong tenfold, silently
-        if type(a).__module__.split('.')[0] == 'ase':
-            raise ValueError(f'system {b} is an ase object, whose velocities are in ASE units, not A/fs: pass velocities= in A/fs '
-                             '(get_velocities() * ase.units.fs) explicitly, and divide what is written back by ase.units.fs')
-    vels = [a.get_velocities() if hasattr(a, 'get_velocities') else None for a in atoms_list]
-    if any(v is None for v in vels):
-        return kw
-    return dict(kw, velocities=[np.asarray(v, np.float64) for v in vels])
-
-
-class SevenNetCalculator(Calculator):
+class SevenNetCalculator(ManyAtomsMixin, Calculator):
     """Supporting properties: 'free_energy', 'energy', 'forces', 'stress', 'stresses', 'energies'."""
 
     implemented_properties = ['free_energy', 'energy', 'forces', 'stress', 'stresses', 'energies']
@@ -323,24 +292,14 @@ class SevenNetCalculator(Calculator):
         optimizer state stay on the GPU from the first step to the last, converged systems stop moving at once and leave the
         batch when enough have finished.  One dict per system, in the given order: the keys of `compute` (evaluated at the
         returned positions) plus `positions` [n,3] fp64, `converged` (largest atomic force below fmax, eV/A) and `n_steps`.
-        A system that is not converged after `steps` steps is returned with converged = False.  kw: repack_below and the
-        FIRE parameters (relax.FIRE_DEFAULTS).  The call's counters are kept as `self.relax_info`."""
+        A system that is not converged after `steps` steps is returned with converged = False.  kw: repack_below, extra (as
+        relax_batch) and the FIRE parameters (relax.FIRE_DEFAULTS).  The call's counters are kept as `self.relax_info`."""
         from .relax import relax_batch
         if len(numbers_list) != len(positions_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
         results, self.relax_info = relax_batch(self.model, self._types_list(numbers_list), list(positions_list), cells, pbcs,
                                                cutoff=self.cutoff, fmax=fmax, steps=steps,
                                                want_atomic_virial=self.compute_atomic_virial, **kw)
-        return results
-
-    def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
-        """`relax_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc / set_positions): the
-        relaxed positions are written back with `set_positions`"""
-        from .d3 import _atoms_args
-        atoms_list = list(atoms_list)
-        results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
-        for a, r in zip(atoms_list, results):
-            a.set_positions(r['positions'])
         return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
@@ -359,31 +318,6 @@ class SevenNetCalculator(Calculator):
                                          pbcs, cutoff=self.cutoff, dt=dt, steps=steps,
                                          want_atomic_virial=self.compute_atomic_virial, **kw)
         return results
-
-    def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
-        """`md_many` over ASE-like objects (get_atomic_numbers / get_positions / get_masses / get_cell / get_pbc, and
-        get_velocities where the object has velocities): positions and velocities are written back with `set_positions` /
-        `set_velocities`.  Velocities at this surface are in A/fs, read and written as they are.  ASE's own time unit is
-        A sqrt(amu / eV) = 10.1805 fs, so the velocities of a real ase.Atoms are in A / (10.1805 fs): multiply
-        get_velocities() by ase.units.fs (0.0982269) on the way in and divide by it on the way out, or pass
-        `velocities=` in A/fs yourself (it takes precedence over the objects').  Because the mistake would be silent, objects of
-        the ase package are refused (ValueError) unless `velocities=` is passed."""
-        from .d3 import _atoms_args
-        atoms_list = list(atoms_list)
-        numbers, positions, cells, pbcs = _atoms_args(atoms_list)
-        results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
-                               **atoms_velocities(atoms_list, kw))
-        for a, r in zip(atoms_list, results):
-            a.set_positions(r['positions'])
-            a.set_velocities(r['velocities'])
-        return results
-
-    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
-        """`compute_many` over ASE-like objects (anything with get_atomic_numbers / get_positions / get_cell / get_pbc)"""
-        atoms_list = list(atoms_list)
-        return self.compute_many([a.get_atomic_numbers() for a in atoms_list], [a.get_positions() for a in atoms_list],
-                                 np.array([np.array(a.get_cell(), np.float64).reshape(3, 3) for a in atoms_list]).reshape(-1, 3, 3),
-                                 np.array([np.asarray(a.get_pbc(), bool).reshape(3) for a in atoms_list]).reshape(-1, 3))
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         Calculator.calculate(self, atoms, properties, system_changes)

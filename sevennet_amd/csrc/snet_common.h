@@ -194,6 +194,26 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double (*sm)[4]) {
   for (int c = 0; c < NV; ++c) v[c] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
   __syncthreads();
 }
+// atoms [a0, a1) of system s of a batch of n atoms, clamped to [0, n] (the same kernels)
+struct Segment {
+  int64_t a0, a1;
+};
+__device__ __forceinline__ Segment segment(const int32_t *__restrict__ seg_ptr, int s, int64_t n) {
+  int64_t a0 = seg_ptr[s], a1 = seg_ptr[s + 1];
+  a0 = a0 < 0 ? 0 : (a0 > n ? n : a0);
+  a1 = a1 > n ? n : (a1 < a0 ? a0 : a1);
+  return Segment{a0, a1};
+}
+// force on atom i in fp64: the model's fp32 forces[3 i + k] widened, plus the fp64 forces_extra[3 i + k] when there is one
+__device__ __forceinline__ void load_force(const float *__restrict__ forces, const double *__restrict__ forces_extra, int64_t i,
+                                           double (&F)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) F[k] = (double)forces[3 * i + k];
+  if (forces_extra) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) F[k] += forces_extra[3 * i + k];
+  }
+}
 
 // ---- cross-lane exchange at VALU speed (no LDS): gfx950 permlane swaps + DPP -------------------
 // a + b where the "low" lanes (bit 5 / bit 4 of the lane id clear) end up with a_self + a_partner

@@ -52,15 +52,8 @@ __device__ __forceinline__ void normals3(uint64_t seed, uint32_t a, uint32_t sys
   xi[2] = r1 * cos(TWO_PI * u[3]);
 }
 
-struct Segment {
-  int64_t a0, a1;
-};
-__device__ __forceinline__ Segment segment(const int32_t *__restrict__ seg_ptr, int s, int64_t n) {
-  int64_t a0 = seg_ptr[s], a1 = seg_ptr[s + 1];
-  a0 = a0 < 0 ? 0 : (a0 > n ? n : a0);
-  a1 = a1 > n ? n : (a1 < a0 ? a0 : a1);
-  return Segment{a0, a1};
-}
+using snet::Segment;   // a system's clamped atom range (snet_common.h)
+using snet::segment;
 
 __global__ __launch_bounds__(MD_THREADS) void mdb_step_kernel(double *__restrict__ pos, double *__restrict__ vel,
                                                                const float *__restrict__ forces, const double *__restrict__ forces_extra,
@@ -82,14 +75,7 @@ __global__ __launch_bounds__(MD_THREADS) void mdb_step_kernel(double *__restrict
     const double m = mass[i];
     double v[3] = {vel[3 * i + 0], vel[3 * i + 1], vel[3 * i + 2]};
     double F[3] = {0.0, 0.0, 0.0};
-    if (phase != 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) F[k] = (double)forces[3 * i + k];
-      if (forces_extra) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) F[k] += forces_extra[3 * i + k];
-      }
-    }
+    if (phase != 0) snet::load_force(forces, forces_extra, i, F);
     if (finish) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;

@@ -27,16 +27,8 @@ __device__ __forceinline__ double wave_max_d(double v) {
   return v;
 }
 
-using snet::block_sum;   // per-system sums in a fixed order (snet_common.h)
-
-__device__ __forceinline__ void load_force(const float *__restrict__ f, const double *__restrict__ fx, int64_t i, double (&F)[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) F[k] = (double)f[3 * i + k];
-  if (fx) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) F[k] += fx[3 * i + k];
-  }
-}
+using snet::block_sum;    // per-system sums in a fixed order (snet_common.h)
+using snet::load_force;   // fp32 forces + optional fp64 forces_extra, in fp64
 
 __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restrict__ pos, double *__restrict__ vel,
                                                                  const float *__restrict__ forces, const double *__restrict__ forces_extra,
@@ -51,9 +43,8 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
   const int tid = threadIdx.x;
   bool still_active = false;
   if (active_s[s] == 1) {   // (uniform over the workgroup)
-    int64_t a0 = seg_ptr[s], a1 = seg_ptr[s + 1];
-    a0 = a0 < 0 ? 0 : (a0 > n ? n : a0);
-    a1 = a1 > n ? n : (a1 < a0 ? a0 : a1);
+    const snet::Segment seg = snet::segment(seg_ptr, s, n);
+    const int64_t a0 = seg.a0, a1 = seg.a1;
     // pass 1: max |F_i|^2, F.v, |F|^2, |v|^2
     double f2max = 0.0;
     double acc[3] = {0.0, 0.0, 0.0};

@@ -14,6 +14,8 @@ from typing import Any, Dict, List, NamedTuple
 import numpy as np
 
 from . import _lib
+from .atoms import HAVE_ASE, Calculator, ManyAtomsMixin, all_changes
+from .batch import _as_host, _normalize, system_of
 
 AU_TO_ANG = 0.52917726
 _BLOB = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'd3_params.npz')
@@ -51,7 +53,6 @@ def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float,
     arrays together with n_atoms[B] (the shape rules of SevenNetCalculator.compute_many); cells[B,3,3] (rows = lattice
     vectors), pbcs[B,3] or one [3].  Applies `molecule_box` per system.  Raises ValueError on an empty batch or system,
     mismatched lengths, Z outside 1..94 and a cell that is singular after the box rule."""
-    from .batch import _as_host, _normalize
     numbers, positions, n_at, cells, pbcs = _normalize(numbers, positions, cells, pbcs, n_atoms)
     numbers = _as_host(numbers, np.int64).reshape(-1)
     positions = np.ascontiguousarray(_as_host(positions, np.float64).reshape(-1, 3))
@@ -61,8 +62,7 @@ def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float,
     bad = (numbers < 1) | (numbers > 94)
     if bad.any():
         i = int(np.nonzero(bad)[0][0])
-        raise ValueError(f'system {int(np.searchsorted(atom_ptr, i, side="right")) - 1}: Z = {int(numbers[i])} '
-                         'has no D3 parameters (Z = 1 .. 94)')
+        raise ValueError(f'system {system_of(atom_ptr, i)}: Z = {int(numbers[i])} has no D3 parameters (Z = 1 .. 94)')
     B = len(n_at)
     cells_out, pbcs_out = np.empty((B, 3, 3)), np.empty((B, 3), np.int32)
     for b in range(B):
@@ -71,20 +71,6 @@ def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float,
             raise ValueError(f'system {b}: singular cell {cell.tolist()} (pbc {pbc.tolist()})')
         cells_out[b], pbcs_out[b] = cell, pbc
     return D3Batch(atom_ptr, np.ascontiguousarray(numbers, np.int32), positions, cells_out, pbcs_out)
-
-
-def _as_host_f64(x) -> np.ndarray:
-    from .batch import _as_host
-    return _as_host(x, np.float64)
-
-
-def _atoms_args(atoms_list):
-    """(numbers_list, positions_list, cells[B,3,3], pbcs[B,3]) of ASE-like objects (get_atomic_numbers / get_positions /
-    get_cell / get_pbc)"""
-    atoms_list = list(atoms_list)
-    return ([a.get_atomic_numbers() for a in atoms_list], [a.get_positions() for a in atoms_list],
-            np.array([np.array(a.get_cell(), np.float64).reshape(3, 3) for a in atoms_list]).reshape(-1, 3, 3),
-            np.array([np.asarray(a.get_pbc(), bool).reshape(3) for a in atoms_list]).reshape(-1, 3))
 
 
 class D3Engine:
@@ -151,22 +137,31 @@ class D3Engine:
             pass
 
 
-try:  # ASE is optional (absent in the offline image): the classes below then expose compute() only
-    from ase.calculators.calculator import Calculator, all_changes
-    _HAVE_ASE = True
-except Exception:  # noqa: BLE001
-    _HAVE_ASE = False
-    all_changes = None
+class D3Term:
+    """The D3 forces and energies as the `extra` of a batched driver (batch.BatchForces): one `D3Engine.compute_many` per
+    call over the systems `ids` at the driver's positions.  numbers flat [N], n_atoms [B]; cells [B,3,3] and pbcs [B,3] (or one
+    [3]) as the caller gave them -- the molecule box is applied by `compute_many`, from the positions of each call.  The batch is
+    prepared on the host, so each call copies the positions down and the forces up.  `last`: the per-system results of the
+    last call."""
 
-    class Calculator:  # minimal stand-in with the attributes the calculators use
-        def __init__(self, **kwargs):
-            self.results = {}
+    def __init__(self, d3_engine: D3Engine, numbers, n_atoms, cells, pbcs):
+        self.engine = d3_engine
+        self.numbers, self.n_atoms = _as_host(numbers, np.int64).reshape(-1), _as_host(n_atoms, np.int64).reshape(-1)
+        B = len(self.n_atoms)
+        self.a_ptr = np.concatenate([[0], np.cumsum(self.n_atoms)])
+        self.cells = _as_host(cells, np.float64).reshape(B, 3, 3)
+        self.pbcs = np.broadcast_to(_as_host(pbcs, bool).reshape(-1, 3), (B, 3))
+        self.last: List[Dict[str, Any]] = []
 
-        def calculate(self, atoms=None, properties=None, system_changes=None):
-            self.atoms = atoms
+    def __call__(self, pos, seg_ptr, ids):
+        import torch
+        z = np.concatenate([self.numbers[self.a_ptr[b]:self.a_ptr[b + 1]] for b in ids])
+        self.last = self.engine.compute_many(z, pos.cpu().numpy(), self.cells[ids], self.pbcs[ids], n_atoms=self.n_atoms[ids])
+        return (torch.as_tensor(np.concatenate([r['forces'] for r in self.last])).to(pos.device),
+                torch.as_tensor(np.array([r['energy'] for r in self.last])).to(pos.device))
 
 
-class D3Calculator(Calculator):
+class D3Calculator(ManyAtomsMixin, Calculator):
     """ASE calculator for the D3 van der Waals correction (sevenn/calculator.py:387-618).
     implemented_properties and result conventions as the reference: free_energy = energy (eV), forces (eV/A),
     stress in ASE Voigt order xx, yy, zz, yz, xz, xy (eV/A^3)."""
@@ -193,10 +188,6 @@ class D3Calculator(Calculator):
         """`compute` for B systems in one D3Engine.compute_many call: one dict per system, in the given order"""
         return [self._results(r) for r in self.engine.compute_many(numbers_list, positions_list, cells, pbcs, n_atoms=n_atoms)]
 
-    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
-        """`compute_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc)"""
-        return self.compute_many(*_atoms_args(atoms_list))
-
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):
         Calculator.calculate(self, atoms, properties, system_changes)
         if atoms is None:
@@ -221,13 +212,13 @@ def _d3_pair(model, file_type, device, modal, enable_cueq, enable_flash, enable_
     return sevennet_calc, d3_calc
 
 
-if _HAVE_ASE:
+if HAVE_ASE:
     from ase.calculators.mixing import SumCalculator as _SumBase
 else:
     _SumBase = object
 
 
-class SevenNetD3Calculator(_SumBase):
+class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
     """SevenNet + D3 (sevenn/calculator.py:236-314: a SumCalculator subclass holding the two).  With ASE present this is an
     ase.calculators.mixing.SumCalculator subclass like the reference's; without it, `compute(numbers, positions, cell, pbc)`
     returns the summed results."""
@@ -237,7 +228,7 @@ class SevenNetD3Calculator(_SumBase):
                  functional_name: str = 'pbe', vdw_cutoff: float = 9000, cn_cutoff: float = 1600, **kwargs):
         pair = _d3_pair(model, file_type, device, modal, enable_cueq, enable_flash, enable_oeq, sevennet_config, damping_type,
                         functional_name, vdw_cutoff, cn_cutoff, kwargs)
-        if _HAVE_ASE:
+        if HAVE_ASE:
             super().__init__(list(pair))
         else:
             self.calcs = list(pair)
@@ -262,9 +253,13 @@ class SevenNetD3Calculator(_SumBase):
         a, b = (c.compute_many(numbers_list, positions_list, cells, pbcs) for c in self.calcs)
         return [self._sum(x, y) for x, y in zip(a, b)]
 
-    def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
-        """`compute_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc)"""
-        return self.compute_many(*_atoms_args(atoms_list))
+    def _d3_term(self, numbers_list, positions_list, cells, pbcs) -> D3Term:
+        """the D3 side of a batched driver, validated on the host (Z range, cells after the box rule)"""
+        d3 = self.calcs[1]
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        bt = prepare_d3_batch(numbers_list, positions_list, cells, pbcs, d3.rthr, d3.cnthr)
+        return D3Term(d3.engine, bt.numbers, np.diff(bt.atom_ptr), cells, pbcs)
 
     def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
         """`SevenNetCalculator.relax_many` on the sum of the model's and the D3 forces (sevennet_amd.relax): one dict per
@@ -272,74 +267,23 @@ class SevenNetD3Calculator(_SumBase):
         returned positions, the counters are kept as `self.relax_info`.  `D3Engine.compute_many` prepares its batch on the
         host, so this path copies the positions down and the D3 forces up once per step (the model's forces and the
         optimizer state stay on the device)."""
-        import torch
-        from .relax import attach_relaxed, check_fire_params, fire_loop, validate_relax_inputs
         snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), list(positions_list)
-        if len(numbers_list) != len(positions_list):
-            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
-        repack_below = kw.pop('repack_below', 0.5)
-        params = check_fire_params(fmax, steps, repack_below, kw)
-        types, positions, n_at, cells_n, pbcs_n = validate_relax_inputs(snet._types_list(numbers_list), positions_list, cells, pbcs,
-                                                                        snet.cutoff, snet.model.spec.num_species)
-        numbers = np.concatenate([np.asarray(z, np.int64).reshape(-1) for z in numbers_list])
-        prepare_d3_batch(numbers, _as_host_f64(positions), cells_n, pbcs_n, d3.rthr, d3.cnthr, n_atoms=n_at)   # Z range, cells
-        a_ptr = np.concatenate([[0], np.cumsum(n_at)])
-
-        def d3_forces(pos_dev, seg_ptr_host, ids):
-            z = np.concatenate([numbers[a_ptr[b]:a_ptr[b + 1]] for b in ids])
-            res = d3.engine.compute_many(z, pos_dev.cpu().numpy(), cells_n[ids], pbcs_n[ids], n_atoms=n_at[ids])
-            return torch.as_tensor(np.concatenate([r['forces'] for r in res])).to(pos_dev.device)
-
-        final, n_steps, converged, info = fire_loop(snet.model, types, positions, n_at, cells_n, pbcs_n, cutoff=snet.cutoff, fmax=fmax,
-                                                    steps=steps, repack_below=repack_below, params=params, extra=d3_forces)
-        pos_h = final.cpu().numpy()
-        results = self.compute_many(numbers_list, [pos_h[a_ptr[b]:a_ptr[b + 1]] for b in range(len(n_at))], cells, pbcs)
-        info['n_force_calls'] += 1
-        self.relax_info = info
-        return attach_relaxed(results, final, a_ptr, n_steps, converged)
-
-    def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
-        """`relax_many` over ASE-like objects; the relaxed positions are written back with `set_positions`"""
-        atoms_list = list(atoms_list)
-        results = self.relax_many(*_atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
-        for a, r in zip(atoms_list, results):
-            a.set_positions(r['positions'])
-        return results
+        term = self._d3_term(numbers_list, positions_list, cells, pbcs)
+        results = snet.relax_many(numbers_list, positions_list, cells, pbcs, fmax=fmax, steps=steps, extra=term, **kw)
+        self.relax_info = snet.relax_info
+        at_final = d3.compute_many(numbers_list, [r['positions'] for r in results], cells, pbcs)
+        return [self._sum(a, b) for a, b in zip(results, at_final)]
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
         """`SevenNetCalculator.md_many` on the sum of the model's and the D3 forces (sevennet_amd.md): one dict per system
         with the summed keys of `compute` at the returned positions plus `positions`, `velocities`, `e_pot` (D3 energy
         included), `e_kin`, `temperature` (and `trajectory`); the counters are kept as `self.md_info`.  As in `relax_many`,
         the D3 batch is prepared on the host: this path copies the positions down and the D3 forces up once per step."""
-        import torch
-        snet, d3 = self.calcs
+        snet = self.calcs[0]
         numbers_list, positions_list = list(numbers_list), list(positions_list)
-        if len(numbers_list) != len(positions_list):
-            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
-        numbers = prepare_d3_batch(numbers_list, positions_list, cells, pbcs, d3.rthr, d3.cnthr).numbers   # Z range, cells
-        last_d3: List[Dict[str, Any]] = []
-
-        def d3_forces(pos_dev, seg_ptr_host, slots):
-            last_d3[:] = d3.engine.compute_many(numbers, pos_dev.cpu().numpy(), cells, pbcs, n_atoms=np.diff(seg_ptr_host))
-            dev = pos_dev.device
-            return (torch.as_tensor(np.concatenate([r['forces'] for r in last_d3])).to(dev),
-                    torch.as_tensor(np.array([r['energy'] for r in last_d3])).to(dev))
-
-        results = snet.md_many(numbers_list, positions_list, masses_list, cells, pbcs, dt, steps, extra=d3_forces, **kw)
+        term = self._d3_term(numbers_list, positions_list, cells, pbcs)
+        results = snet.md_many(numbers_list, positions_list, masses_list, cells, pbcs, dt, steps, extra=term, **kw)
         self.md_info = snet.md_info
         # the model's results and the D3 results of the last step's evaluations, both at the returned positions
-        return [self._sum(a, D3Calculator._results(b)) for a, b in zip(results, last_d3)]
-
-    def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
-        """`md_many` over ASE-like objects, as SevenNetCalculator.md_many_atoms (velocities in A/fs, see there): positions
-        and velocities are written back with `set_positions` / `set_velocities`"""
-        from .calculator import atoms_velocities
-        atoms_list = list(atoms_list)
-        numbers, positions, cells, pbcs = _atoms_args(atoms_list)
-        results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
-                               **atoms_velocities(atoms_list, kw))
-        for a, r in zip(atoms_list, results):
-            a.set_positions(r['positions'])
-            a.set_velocities(r['velocities'])
-        return results
+        return [self._sum(a, D3Calculator._results(b)) for a, b in zip(results, term.last)]

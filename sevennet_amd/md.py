@@ -14,7 +14,6 @@ depend on the batch it runs in.  The rule is written out in include/snet_hip.h (
 tests/md_ref.py.  Units: eV, A, fs, amu, K."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -22,8 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _as_host, batch_results, build_batch_graph
-from .relax import validate_relax_inputs
+from .batch import BatchForces, _as_host, batch_results, system_of, validate_batch_inputs
 
 ACC = 9.648533212e-3    # eV / (A amu) in A / fs^2
 KB = 8.617333262e-5     # eV / K
@@ -34,10 +32,6 @@ def langevin_coefficients(friction: float, dt: float) -> Tuple[float, float]:
     """(c1, c2) = (exp(-gamma dt), sqrt(1 - c1^2)) in fp64 on the host: what snet_mdb_step is given (friction 0: (1, 0), NVE)"""
     c1 = math.exp(-float(friction) * float(dt))
     return c1, math.sqrt(1.0 - c1 * c1)
-
-
-def _system_of(a_ptr: np.ndarray, row: int) -> int:
-    return int(np.searchsorted(a_ptr, row, side='right')) - 1
 
 
 def _per_atom(x, n_at: np.ndarray, width: int, what: str) -> np.ndarray:
@@ -63,7 +57,7 @@ def _per_atom(x, n_at: np.ndarray, width: int, what: str) -> np.ndarray:
 
 def validate_md_inputs(masses, n_at: np.ndarray, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
                        system_ids=None):
-    """Host checks of everything md_batch takes beyond the relax inputs -> (mass fp64 [N], velocities fp64 [N,3] or None, kT
+    """Host checks of everything md_batch takes beyond the batch inputs (`validate_batch_inputs`) -> (mass fp64 [N], velocities fp64 [N,3] or None, kT
     fp64 [B] in eV, system ids int32 [B]).  ValueError names the system."""
     B = len(n_at)
     a_ptr = np.concatenate([[0], np.cumsum(n_at)])
@@ -101,13 +95,13 @@ def validate_md_inputs(masses, n_at: np.ndarray, dt, steps, temperature, frictio
     bad = ~((mass > 0) & np.isfinite(mass))
     if bad.any():
         i = int(np.nonzero(bad)[0][0])
-        raise ValueError(f'system {_system_of(a_ptr, i)}: mass = {mass[i]} amu, finite masses > 0 are required')
+        raise ValueError(f'system {system_of(a_ptr, i)}: mass = {mass[i]} amu, finite masses > 0 are required')
     vel = None
     if velocities is not None:
         vel = _per_atom(velocities, n_at, 3, 'velocities')
         fin = np.isfinite(vel).all(1)
         if not fin.all():
-            raise ValueError(f'system {_system_of(a_ptr, int(np.nonzero(~fin)[0][0]))}: non-finite velocity')
+            raise ValueError(f'system {system_of(a_ptr, int(np.nonzero(~fin)[0][0]))}: non-finite velocity')
     if system_ids is None:
         ids = np.arange(B, dtype=np.int64)
     else:
@@ -115,16 +109,6 @@ def validate_md_inputs(masses, n_at: np.ndarray, dt, steps, temperature, frictio
         if len(ids) != B or (ids < 0).any() or (ids >= 2 ** 31).any():
             raise ValueError(f'system_ids: {B} integers in [0, 2^31) are required')
     return mass, vel, kT, ids.astype(np.int32)
-
-
-def _check_tensors(name: str, ref: torch.Tensor, want) -> None:
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != ref.device or not t.is_cuda:
-            raise ValueError(f'{name}: a contiguous {dtype} tensor of shape {shape} on {ref.device} is required, got '
-                             f'{t.dtype} {tuple(t.shape)} on {t.device}')
-
-
-_P = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
 
 
 def md_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor,
@@ -138,43 +122,43 @@ def md_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, mass: to
             (e_kin, torch.float64, (B,))]
     if forces_extra is not None:
         want.append((forces_extra, torch.float64, (N, 3)))
-    _check_tensors('md_step', pos, want)
+    _lib.check_device_tensors('md_step', pos, want)
+    P = _lib.ptr
     with torch.cuda.device(pos.device):
         _lib.check(_lib.load().snet_mdb_step(
-            _P(pos), _P(vel), _P(forces), _P(forces_extra), _P(mass), N, _P(seg_ptr), _P(sys_id), B, _P(kT), _P(step_index), _P(e_kin),
-            float(dt), float(c1), float(c2), int(seed), int(phase), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-            'snet_mdb_step')
+            P(pos), P(vel), P(forces), P(forces_extra), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), P(step_index), P(e_kin),
+            float(dt), float(c1), float(c2), int(seed), int(phase), _lib.stream()), 'snet_mdb_step')
 
 
 def init_velocities(vel: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor, sys_id: torch.Tensor, kT: torch.Tensor,
                     seed: int, remove_com: bool = True) -> None:
     """one `snet_mdb_init_velocities` launch on the current stream: Maxwell-Boltzmann velocities at kT (eV) into vel"""
     N, B = int(vel.shape[0]), int(seg_ptr.numel()) - 1
-    _check_tensors('init_velocities', vel, [(vel, torch.float64, (N, 3)), (mass, torch.float64, (N,)), (seg_ptr, torch.int32, (B + 1,)),
-                                            (sys_id, torch.int32, (B,)), (kT, torch.float64, (B,))])
+    _lib.check_device_tensors('init_velocities', vel, [(vel, torch.float64, (N, 3)), (mass, torch.float64, (N,)),
+                                                       (seg_ptr, torch.int32, (B + 1,)), (sys_id, torch.int32, (B,)),
+                                                       (kT, torch.float64, (B,))])
+    P = _lib.ptr
     with torch.cuda.device(vel.device):
-        _lib.check(_lib.load().snet_mdb_init_velocities(
-            _P(vel), _P(mass), N, _P(seg_ptr), _P(sys_id), B, _P(kT), int(seed), int(bool(remove_com)),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'snet_mdb_init_velocities')
+        _lib.check(_lib.load().snet_mdb_init_velocities(P(vel), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), int(seed),
+                                                        int(bool(remove_com)), _lib.stream()), 'snet_mdb_init_velocities')
 
 
-def md_loop(engine, types: np.ndarray, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray,
-            n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, *, cutoff: float, dt: float, steps: int, friction: float,
-            seed: int, log_every: int, traj_every: int, remove_com: bool, extra: Optional[Callable], want_atomic_virial: bool):
-    """The MD loop on validated inputs (`validate_relax_inputs`, `validate_md_inputs`) -> (graph and engine output of the last
-    force call, dict of device tensors: pos, vel [N,3], e_pot, e_kin [samples,B], traj [frames,N,3] or None, step_index [B]; info)"""
-    dev = engine.dev
-    ns = engine.spec.num_species
+def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray, *,
+            dt: float, steps: int, friction: float, seed: int, log_every: int, traj_every: int, remove_com: bool,
+            want_atomic_virial: bool):
+    """The MD loop over the force call `forces` (a BatchForces on validated inputs; `validate_md_inputs`) -> (graph and engine
+    output of the last force call, dict of device tensors: pos, vel [N,3], e_pot, e_kin [samples,B], traj [frames,N,3] or None,
+    step_index [B]; info)"""
+    dev = forces.engine.dev
+    n_atoms = forces.n_atoms
     B, steps, log_every, traj_every = len(n_atoms), int(steps), int(log_every), int(traj_every)
-    sp_host = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
-    slots = np.arange(B)
     c1, c2 = langevin_coefficients(friction, dt)
     up = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a, dtype)).to(dev)  # noqa: E731
     with torch.cuda.device(dev):
         pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
                else up(positions, np.float64)).reshape(-1, 3).clone()
         N = int(pos.shape[0])
-        ty, m_d, kT_d, id_d, seg = up(types, np.int32), up(mass, np.float64), up(kT, np.float64), up(ids, np.int32), up(sp_host, np.int32)
+        m_d, kT_d, id_d, seg = up(mass, np.float64), up(kT, np.float64), up(ids, np.int32), up(forces.a_ptr, np.int32)
         if vel0 is None:
             vel = torch.empty_like(pos)
             init_velocities(vel, m_d, seg, id_d, kT_d, seed, remove_com)
@@ -185,19 +169,10 @@ def md_loop(engine, types: np.ndarray, positions, mass: np.ndarray, vel0: Option
         e_pot_log = torch.zeros(steps // log_every + 1, B, dtype=torch.float64, device=dev)
         e_kin_log = torch.zeros_like(e_pot_log)
         traj = torch.zeros(steps // traj_every + 1, N, 3, dtype=torch.float64, device=dev) if traj_every > 0 else None
-        info = dict(n_force_calls=0, md_launches=0, system_steps_evaluated=0)
         g = out = None
         for k in range(steps + 1):
             last = k == steps
-            g = build_batch_graph(ty, pos, cells, pbcs, cutoff, ns, n_atoms=n_atoms, device=dev, species_rows=engine.needs_species_rows)
-            out = engine.compute(g, want_atomic_virial=want_atomic_virial and last)
-            fx = ex = None
-            if extra is not None:
-                fx = extra(pos, sp_host, slots)
-                if isinstance(fx, tuple):
-                    fx, ex = fx
-                    ex = torch.as_tensor(ex).to(dev, torch.float64).reshape(B)
-                fx = torch.as_tensor(fx).to(dev, torch.float64).contiguous()
+            g, out, fx, ex = forces(pos, want_atomic_virial=want_atomic_virial and last)
             if traj is not None and k % traj_every == 0:
                 traj[k // traj_every].copy_(pos)   # x_k: the launch below moves on to x_{k+1}
             md_step(pos, vel, out['forces'], m_d, seg, id_d, kT_d, step_index, e_kin, dt, c1, c2, seed,
@@ -206,9 +181,7 @@ def md_loop(engine, types: np.ndarray, positions, mass: np.ndarray, vel0: Option
                 j = k // log_every
                 e_pot_log[j].copy_(out['energy_per_system'] if ex is None else out['energy_per_system'] + ex)
                 e_kin_log[j].copy_(e_kin)
-            info['n_force_calls'] += 1
-            info['md_launches'] += 1
-            info['system_steps_evaluated'] += B
+    info = dict(n_force_calls=forces.n_force_calls, md_launches=steps + 1, system_steps_evaluated=forces.system_steps_evaluated)
     return g, out, dict(pos=pos, vel=vel, e_pot=e_pot_log, e_kin=e_kin_log, traj=traj, step_index=step_index), info
 
 
@@ -234,15 +207,15 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
              system_ids=None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
     """`steps` MD steps of `dt` fs for B structures at fixed cells: NVE (friction 0) or Langevin at `temperature`.
 
-    engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `relax_batch`; masses (amu)
+    engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `build_batch_graph`; masses (amu)
     and velocities (A/fs) per system or flat like the positions; the caller's arrays are not modified.  temperature (K): a
     scalar or one value per system; friction: gamma in 1/fs (> 0 needs a temperature).  velocities None: drawn at
     `temperature` on the device (`remove_com`: each system's centre of mass at rest, kinetic energy (3 n - 3) kT / 2
     exactly).  seed: of the noise (thermostat and draw); two runs with one seed give identical bits.  system_ids: the id each
     system's noise is counted under, default 0..B-1 -- a system run alone under the id it had in a batch sees the same noise.
-    extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [B+1] on the host, ids int64 [B]: the index of
-    each system in this call) -> fp64 forces [N,3], or (forces, energy_per_system fp64 [B]), added to the model's each step
-    (the energies go into the potential-energy log).
+    extra: optional callable with the contract of `batch.BatchForces` (positions fp64 [N,3] on the device, seg_ptr int64 [B+1]
+    on the host, ids int64 [B]: the index of each system in this call) -> forces [N,3], or (forces, energy_per_system [B]),
+    added to the model's each step (the energies go into the potential-energy log).
 
     Schedule: F0 = f(x0), one launch that starts step 1; then per step Fk = f(xk) and one launch that finishes step k and
     starts step k + 1 (the last one only finishes).  steps = 0: one force call, one launch that moves nothing.
@@ -252,12 +225,13 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     (2 e_kin / (3 n KB), K) over the logged steps -- sample j belongs to step j log_every -- and `trajectory` [frames,n,3]
     (step j traj_every) when traj_every > 0.  info: n_force_calls == md_launches == steps + 1, system_steps_evaluated ==
     B (steps + 1).  Invalid input raises ValueError before any device work."""
-    types, positions, n_at, cells, pbcs = validate_relax_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
+    types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
     mass, vel0, kT, ids = validate_md_inputs(masses, n_at, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
                                              system_ids)
-    g, out, state, info = md_loop(engine, types, positions, mass, vel0, kT, ids, n_at, cells, pbcs, cutoff=cutoff, dt=dt, steps=steps,
-                                  friction=friction, seed=seed, log_every=log_every, traj_every=traj_every, remove_com=remove_com,
-                                  extra=extra, want_atomic_virial=want_atomic_virial)
+    forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
+    g, out, state, info = md_loop(forces, positions, mass, vel0, kT, ids, dt=dt, steps=steps, friction=friction, seed=seed,
+                                  log_every=log_every, traj_every=traj_every, remove_com=remove_com,
+                                  want_atomic_virial=want_atomic_virial)
     results = batch_results(g, out, cells, want_atomic_virial)
     return attach_md(results, state, g.seg_ptr_host, n_at), info

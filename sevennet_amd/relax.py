@@ -12,14 +12,13 @@ masses; the step rule is written out in include/snet_hip.h (snet_fire_step) and 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .batch import BATCH_MAX_ATOMS, _as_host, _normalize, batch_results, build_batch_graph, classify_systems
+from .batch import BatchForces, batch_results, validate_batch_inputs
 
 FIRE_DEFAULTS = dict(dt_start=0.1, dt_max=1.0, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, max_step=0.2)
 
@@ -47,30 +46,6 @@ def check_fire_params(fmax: float, steps: int, repack_below: float, fire: dict) 
                              '0 < alpha_start <= 1, 0 < f_alpha <= 1, max_step > 0)')
     p['n_min'] = int(p['n_min'])
     return p
-
-
-def validate_relax_inputs(types, positions, cells, pbcs, cutoff: float, num_species: int, n_atoms=None,
-                          max_atoms: int = BATCH_MAX_ATOMS):
-    """Everything `build_batch_graph` would reject, found on the host before the first launch: -> (types int64 [N] on the
-    host, positions [N,3] (host array or the caller's tensor), n_atoms [B], cells [B,3,3], pbcs [B,3]).  ValueError names the
-    system."""
-    types, positions, n_at, cells, pbcs = _normalize(types, positions, cells, pbcs, n_atoms)
-    types = _as_host(types, np.int64).reshape(-1)
-    a_ptr = np.concatenate([[0], np.cumsum(n_at)])
-    bad = (types < 0) | (types >= num_species)
-    if bad.any():
-        i = int(np.nonzero(bad)[0][0])
-        raise ValueError(f'system {int(np.searchsorted(a_ptr, i, side="right")) - 1}: unknown species index {int(types[i])} '
-                         f'(the model has {num_species})')
-    if not isinstance(positions, torch.Tensor):   # (device tensors are not read back for this)
-        fin = np.isfinite(positions).all(1)
-        if not fin.all():
-            i = int(np.nonzero(~fin)[0][0])
-            raise ValueError(f'system {int(np.searchsorted(a_ptr, i, side="right")) - 1}: non-finite position')
-    if not cutoff > 0:
-        raise ValueError(f'cutoff = {cutoff}: a positive cutoff is required')
-    classify_systems(n_at, cells, pbcs, cutoff, max_atoms)   # singular cells
-    return types, positions, n_at, cells, pbcs
 
 
 class RepackBook:
@@ -126,31 +101,24 @@ def fire_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, seg_pt
             (n_steps, torch.int32, (B,)), (fmax_sys, torch.float64, (B,)), (n_active, torch.int32, (1,))]
     if forces_extra is not None:
         want.append((forces_extra, torch.float64, (N, 3)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != pos.device or not t.is_cuda:
-            raise ValueError(f'fire_step: a contiguous {dtype} tensor of shape {shape} on {pos.device} is required, got '
-                             f'{t.dtype} {tuple(t.shape)} on {t.device}')
-    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    _lib.check_device_tensors('fire_step', pos, want)
+    P = _lib.ptr
     with torch.cuda.device(pos.device):
         _lib.check(_lib.load().snet_fire_step(
             P(pos), P(vel), P(forces), P(forces_extra), N, P(seg_ptr), B, P(dt), P(alpha), P(n_pos), P(active), P(n_steps),
             P(fmax_sys), P(n_active), float(fmax), params['dt_start'], params['dt_max'], params['n_min'], params['f_inc'],
-            params['f_dec'], params['alpha_start'], params['f_alpha'], params['max_step'],
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'snet_fire_step')
+            params['f_dec'], params['alpha_start'], params['f_alpha'], params['max_step'], _lib.stream()), 'snet_fire_step')
 
 
-def fire_loop(engine, types: np.ndarray, positions, n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, *, cutoff: float,
-              fmax: float, steps: int, repack_below: float, params: dict, extra: Optional[Callable] = None):
-    """The relaxation loop on validated inputs (`validate_relax_inputs`, `check_fire_params`): -> (positions fp64 [N,3] on the
-    device in the caller's order, n_steps [B], converged [B], info)"""
-    dev = engine.dev
-    ns = engine.spec.num_species
-    book = RepackBook(n_atoms)
+def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack_below: float, params: dict):
+    """The relaxation loop over the force call `forces` (a BatchForces on validated inputs; `check_fire_params`): -> (positions
+    fp64 [N,3] on the device in the caller's order, n_steps [B], converged [B], info)"""
+    dev = forces.engine.dev
+    book = RepackBook(forces.n_atoms)
     B = book.B
     with torch.cuda.device(dev):
         pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
                else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).clone()
-        ty = torch.as_tensor(types.astype(np.int32)).to(dev)
         vel = torch.zeros_like(pos)
         dt = torch.full((B,), float(params['dt_start']), dtype=torch.float64, device=dev)
         alpha = torch.full((B,), float(params['alpha_start']), dtype=torch.float64, device=dev)
@@ -159,33 +127,25 @@ def fire_loop(engine, types: np.ndarray, positions, n_atoms: np.ndarray, cells: 
         n_steps = torch.zeros(B, dtype=torch.int32, device=dev)
         fmax_sys = torch.zeros(B, dtype=torch.float64, device=dev)
         n_active = torch.zeros(1, dtype=torch.int32, device=dev)
-        info = dict(n_force_calls=0, n_repacks=0, system_steps_evaluated=0, fire_launches=0)
+        fire_launches = 0
         for _ in range(int(steps)):
-            ids = book.ids
-            sp_host = book.seg_ptr()
-            g = build_batch_graph(ty, pos, cells[ids], pbcs[ids], cutoff, ns, n_atoms=n_atoms[ids], device=dev,
-                                  species_rows=engine.needs_species_rows)
-            out = engine.compute(g)
-            fx = None
-            if extra is not None:
-                fx = extra(pos, sp_host, ids).to(dev, torch.float64).contiguous()
+            g, out, fx = forces(pos, book.ids)[:3]   # (FIRE has no use for the extra energies)
             fire_step(pos, vel, out['forces'], g.seg_ptr, dt, alpha, n_pos, active, n_steps, fmax_sys, n_active, fmax, params, fx)
-            info['n_force_calls'] += 1
-            info['fire_launches'] += 1
-            info['system_steps_evaluated'] += len(ids)
+            fire_launches += 1
             left = int(n_active.item())   # the one readback of the step
             if left == 0:
                 break
-            if book.wants_repack(left, len(ids), repack_below):
+            if book.wants_repack(left, len(book.ids), repack_below):
                 act_h, st_h = torch.stack([active, n_steps]).cpu().numpy()
                 keep, rows = book.repack(pos, act_h, st_h)
                 rows_d, keep_d = torch.as_tensor(rows).to(dev), torch.as_tensor(keep).to(dev)
-                pos, vel, ty = pos[rows_d], vel[rows_d], ty[rows_d]   # (gathers copy: the stored slices keep the old buffer)
+                pos, vel = pos[rows_d], vel[rows_d]   # (gathers copy: the stored slices keep the old buffer)
                 dt, alpha, n_pos, active, n_steps, fmax_sys = (t[keep_d] for t in (dt, alpha, n_pos, active, n_steps, fmax_sys))
         act_h, st_h = torch.stack([active, n_steps]).cpu().numpy()
         book.store(pos, act_h, st_h, only_finished=False)
-        info['n_repacks'] = book.n_repacks
         final = torch.cat(book.positions)
+    info = dict(n_force_calls=forces.n_force_calls, n_repacks=book.n_repacks, system_steps_evaluated=forces.system_steps_evaluated,
+                fire_launches=fire_launches)
     return final, book.n_steps.copy(), book.converged.copy(), info
 
 
@@ -197,9 +157,9 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
     engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `build_batch_graph`; the
     caller's arrays are not modified.  repack_below: when at most this fraction of the current batch is still active (and a
     system has finished since the batch was built) the batch is rebuilt from the active systems; 0 never repacks.
-    extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [b+1] on the host, ids int64 [b]: the caller's
-    index of each system of the current batch) -> fp64 forces [N,3] added to the model's each step.  fire: FIRE_DEFAULTS
-    overrides.
+    extra: optional callable with the contract of `batch.BatchForces` (positions fp64 [N,3] on the device, seg_ptr int64
+    [b+1] on the host, ids int64 [b]: the caller's index of each system of the current batch) -> forces [N,3], or (forces,
+    energy_per_system [b]), added to the model's each step (FIRE has no use for the energies).  fire: FIRE_DEFAULTS overrides.
 
     Returns (results, info).  results[b]: the dict of SevenNetCalculator.compute_many from ONE batched evaluation of all B
     systems at their final positions, plus `positions` [n,3] fp64, `converged` and `n_steps` (the moves made).  A system is
@@ -208,14 +168,12 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
     fire_launches (= loop iterations), system_steps_evaluated (systems in the batch, summed over the loop's engine calls),
     n_repacks.  Invalid input raises ValueError before any device work."""
     params = check_fire_params(fmax, steps, repack_below, fire)
-    types, positions, n_at, cells, pbcs = validate_relax_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
+    types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
-    final, n_steps, converged, info = fire_loop(engine, types, positions, n_at, cells, pbcs, cutoff=cutoff, fmax=fmax, steps=steps,
-                                                repack_below=repack_below, params=params, extra=extra)
-    g = build_batch_graph(torch.as_tensor(types.astype(np.int32)).to(engine.dev), final, cells, pbcs, cutoff, engine.spec.num_species,
-                          n_atoms=n_at, device=engine.dev, species_rows=engine.needs_species_rows)
-    out = engine.compute(g, want_atomic_virial=want_atomic_virial)
-    info['n_force_calls'] += 1
+    forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
+    final, n_steps, converged, info = fire_loop(forces, positions, fmax=fmax, steps=steps, repack_below=repack_below, params=params)
+    g, out, _, _ = forces(final, want_atomic_virial=want_atomic_virial, with_extra=False)
+    info['n_force_calls'] = forces.n_force_calls
     results = batch_results(g, out, cells, want_atomic_virial)
     return attach_relaxed(results, final, g.seg_ptr_host, n_steps, converged), info
 

@@ -37,6 +37,19 @@ def synthetic_system(n_rep=(2, 2, 2), a=5.431, sigma=0.05, seed=0, cutoff=5.0, n
     return types, pos, cell, ei, ev
 
 
+def three_small_systems(seed=0):
+    """B = 3 systems of 2, 5 and 8 atoms as (species indices in {0, 1}, positions, cell, pbc): a periodic cell of 6 A, a molecule
+    with a zero cell, a slab with pbc (T, T, F) -- the smallest sizes at which the segment arithmetic, a subset of the systems
+    and the molecule box can each still go wrong"""
+    from sevennet_amd.neighbor import diamond_cubic
+    rng = np.random.default_rng(seed)
+    mol = np.array([[0.0, 0.0, 0.0], [1.1, 0.0, 0.0], [-0.4, 1.0, 0.0], [0.2, -0.5, 1.0], [2.3, 0.4, -0.6]])
+    slab, cell = diamond_cubic(5.431, (1, 1, 1), 0.08, seed)
+    return [(np.array([0, 1]), np.array([[0.5, 0.4, 0.3], [2.1, 1.0, 0.7]]) + rng.normal(0, 0.05, (2, 3)), np.eye(3) * 6.0, [True] * 3),
+            (np.array([0, 1, 1, 0, 1]), mol + rng.normal(0, 0.05, (5, 3)), np.zeros((3, 3)), [False] * 3),
+            (rng.integers(0, 2, 8), slab, cell, [True, True, False])]
+
+
 def packed_tiles_expected(row_ptr, lo, hi, group=8):
     """restatement of snet_edge_tiles_packed: greedy windows of <= 16 consecutive edges over <= 2 rows, per group of rows"""
     rp = [int(v) for v in row_ptr]

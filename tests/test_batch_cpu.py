@@ -130,3 +130,36 @@ def test_stress_conversion_by_hand():
     # the TorchSim mapping: stress = -voigt_6_to_full_3x3((virial / V)[[0,1,2,4,5,3]]) is the same tensor
     ts = -voigt_to_3x3(torch.tensor(vir[:1] / 24.0)[..., [0, 1, 2, 4, 5, 3]])
     assert np.allclose(ts[0].numpy(), m)
+
+
+def test_system_of_at_the_ends_of_every_system():
+    from sevennet_amd.batch import system_of
+    a_ptr = np.array([0, 2, 3, 8, 9])   # systems of 2, 1, 5 and 1 atoms
+    for b in range(4):
+        assert system_of(a_ptr, a_ptr[b]) == b and system_of(a_ptr, a_ptr[b + 1] - 1) == b
+    assert [system_of(a_ptr, i) for i in range(9)] == [0, 0, 1, 2, 2, 2, 2, 2, 3] and type(system_of(a_ptr, 4)) is int
+
+
+def test_validate_batch_inputs_names_the_system():
+    """the six messages of test_relax_cpu's bad-systems test, from the function itself"""
+    from sevennet_amd.batch import validate_batch_inputs
+    types = [np.array([0, 1]), np.array([1])]
+    pos = [np.array([[0.0, 0, 0], [1.2, 0, 0]]), np.array([[0.0, 0, 0]])]
+    cells = np.stack([np.eye(3) * 6.0, np.zeros((3, 3))])
+    pbcs = np.array([[True] * 3, [False] * 3])
+    v = lambda t=types, p=pos, c=cells, b=pbcs: validate_batch_inputs(t, p, c, b, 5.0, 2)   # noqa: E731
+    with pytest.raises(ValueError, match='system 1: unknown species index 2'):
+        v(t=[types[0], np.array([2])])
+    with pytest.raises(ValueError, match='system 0: singular cell'):
+        v(c=np.stack([np.diag([6.0, 6.0, 0.0]), np.zeros((3, 3))]))
+    with pytest.raises(ValueError, match='system 1: 1 types but 2 positions'):
+        v(p=[pos[0], np.zeros((2, 3))])
+    with pytest.raises(ValueError, match='system 1 has no atoms'):
+        v(t=[types[0], np.zeros(0, np.int64)], p=[pos[0], np.zeros((0, 3))])
+    with pytest.raises(ValueError, match='system 0: non-finite position'):
+        v(p=[np.array([[0.0, 0, 0], [np.nan, 0, 0]]), pos[1]])
+    with pytest.raises(ValueError, match='empty batch'):
+        v(t=[], p=[], c=np.zeros((0, 3, 3)), b=np.zeros((0, 3), bool))
+    ty, p, n_at, c, b = v()   # and what it returns for a good batch
+    assert ty.tolist() == [0, 1, 1] and ty.dtype == np.int64 and p.shape == (3, 3) and n_at.tolist() == [2, 1]
+    assert c.shape == (2, 3, 3) and b.shape == (2, 3) and b.dtype == bool

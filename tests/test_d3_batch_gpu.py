@@ -103,6 +103,34 @@ def test_deterministic_and_order_preserving():
         _assert_equal(a[k], r[k], f'reversed {k}')
 
 
+def test_d3_term_is_one_compute_many_over_the_systems_asked_for():
+    """the `extra` of the batched drivers: systems [2, 0] of the three small systems at perturbed positions (the molecule's box
+    comes from those positions, not from the ones the term was built with)"""
+    import torch
+    from helpers import three_small_systems
+    from sevennet_amd.d3 import D3Term
+    eng = _engine('damp_bj', 'pbe', *CUT)
+    systems = three_small_systems()
+    z = [np.array([14, 8])[s[0]] for s in systems]
+    term = D3Term(eng, np.concatenate(z), [len(s[0]) for s in systems], np.stack([s[2] for s in systems]),
+                  np.array([s[3] for s in systems]))
+    rng = np.random.default_rng(4)
+    for ids in ([2, 0], [1]):
+        moved = [systems[b][1] + rng.normal(0, 0.1, systems[b][1].shape) for b in ids]
+        pos = torch.as_tensor(np.concatenate(moved)).to('cuda:0')
+        seg_ptr = np.concatenate([[0], np.cumsum([len(m) for m in moved])])
+        forces, energies = term(pos, seg_ptr, np.array(ids))
+        want = eng.compute_many([z[b] for b in ids], moved, np.stack([systems[b][2] for b in ids]), np.array([systems[b][3] for b in ids]))
+        assert forces.device == pos.device and energies.device == pos.device
+        assert forces.dtype == torch.float64 and energies.dtype == torch.float64
+        assert np.array_equal(forces.cpu().numpy(), np.concatenate([w['forces'] for w in want]))
+        assert energies.cpu().numpy().tolist() == [w['energy'] for w in want]
+        assert len(term.last) == len(ids)
+        for got, w in zip(term.last, want):
+            _assert_equal(got, w, f'systems {ids}')
+    assert np.abs(term.last[0]['forces']).max() > 0   # the molecule: its box did not turn the term off
+
+
 def test_a_large_cell_among_small_ones():
     """1 000 Si atoms (t_chunks = 1) beside cells of 1 .. 64 atoms (t_chunks > 1): each keeps its own traversal"""
     from sevennet_amd.neighbor import diamond_cubic

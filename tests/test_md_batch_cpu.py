@@ -196,6 +196,21 @@ def test_bad_input_raises_before_any_device_work(monkeypatch, kw, match):
         _md(monkeypatch, **kw)
 
 
+def test_batch_forces_is_constructed_without_any_device_work(monkeypatch):
+    """BatchForces on the engine that may not be touched, with torch.cuda.device / current_stream / synchronize raising"""
+    import torch
+    from sevennet_amd.batch import BatchForces, validate_batch_inputs
+
+    def touched(*a, **k):
+        raise AssertionError('torch.cuda was touched by the constructor')
+    for name in ('device', 'current_stream', 'synchronize'):
+        monkeypatch.setattr(torch.cuda, name, touched)
+    types, pos, _, cells, pbcs = _two_systems()
+    ty, _, n_at, cells, pbcs = validate_batch_inputs(types, pos, cells, pbcs, 5.0, 2)
+    forces = BatchForces(_NoDeviceEngine(), ty, n_at, cells, pbcs, 5.0, extra=lambda *a: None)
+    assert (forces.n_force_calls, forces.system_steps_evaluated) == (0, 0)
+
+
 def test_validated_inputs_are_copies_in_the_stated_units():
     from sevennet_amd.md import ACC, KB, langevin_coefficients, validate_md_inputs
     assert (ACC, KB) == (md_ref.ACC, md_ref.KB)
@@ -224,7 +239,7 @@ def test_surfaces_exist():
 
 def test_ase_objects_are_refused_without_explicit_velocities():
     """their velocity unit is A / (10.18 fs): read as A/fs it would be wrong tenfold without a sign of it"""
-    from sevennet_amd.calculator import atoms_velocities
+    from sevennet_amd.atoms import atoms_velocities
 
     class Duck:
         def __init__(self, v):

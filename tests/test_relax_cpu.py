@@ -72,6 +72,21 @@ def test_bad_systems_raise_before_any_device_work_and_name_the_system():
         _relax(types=[], positions=[], cells=np.zeros((0, 3, 3)), pbcs=np.zeros((0, 3), bool))
 
 
+def test_batch_forces_is_constructed_without_any_device_work(monkeypatch):
+    """BatchForces on the engine that may not be touched, with torch.cuda.device / current_stream / synchronize raising"""
+    import torch
+    from sevennet_amd.batch import BatchForces, validate_batch_inputs
+
+    def touched(*a, **k):
+        raise AssertionError('torch.cuda was touched by the constructor')
+    for name in ('device', 'current_stream', 'synchronize'):
+        monkeypatch.setattr(torch.cuda, name, touched)
+    types, pos, cells, pbcs = _two_systems()
+    ty, _, n_at, cells, pbcs = validate_batch_inputs(types, pos, cells, pbcs, 5.0, 2)
+    forces = BatchForces(_NoDeviceEngine(), ty, n_at, cells, pbcs, 5.0, extra=lambda *a: None)
+    assert (forces.n_force_calls, forces.system_steps_evaluated) == (0, 0)
+
+
 def test_restatement_follows_the_rule_on_a_harmonic_well():
     """F = -k r with k = 1 from r0: step 0 has v = 0, so P = 0 and dt halves; then P > 0 until far beyond step n_min + 3 (the
     time integrated, < 0.5, is well short of the quarter period pi / 2), so n_pos counts up, and dt and alpha first change in the
