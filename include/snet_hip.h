@@ -461,6 +461,38 @@ int snet_fire_step(double *pos, double *vel, const float *forces, const double *
                    int32_t *n_steps, double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max,
                    int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step, void *stream);
 
+/* ---- batched variable-cell FIRE relaxation step (unit masses) -----------------------------------
+ * One step of FIRE over the atoms AND the cell of n_sys systems in ONE launch: the rule of ASE's UnitCellFilter (Tadmor et al.,
+ * Phys. Rev. B 59, 235 (1999): atoms in the frame of a reference cell plus the deformation gradient) under the FIRE of
+ * snet_fire_step.  Arrays as snet_fire_step, and per system: cell (fp64 [n_sys,9], row-major lattice vectors, updated in place),
+ * cell0 (the reference cell, read only), vel_cell (fp64 [n_sys,9], updated in place), virial (fp64 [n_sys,6], the engine's
+ * virial_per_system: order xx,yy,zz,xy,yz,zx, stress = -virial / volume; virial_extra, fp64 [n_sys,6] or NULL, is added to it),
+ * status (int32 [n_sys]: the caller's 0 while running, 1 written when converged, 2 when the guard below fails).
+ * For every system with active == 1 and n atoms, in fp64, with C the cell, C0 the reference cell and f the summed forces:
+ *   F = (C0^-1 C)^T  (so C = C0 F^T);  V = |det C|;  W = the symmetric 3x3 of the summed virials - scalar_pressure V I
+ *   cell force:  G = W F^-T;  if hydrostatic_strain: G = I tr(G)/3;  G *= M elementwise, M the symmetric 0/1 matrix of
+ *                cell_mask_bits (bit k = Voigt flag k of xx,yy,zz,yz,xz,xy);  if constant_volume: G -= I tr(G)/3;  G /= n
+ *   atom forces: g_i = f_i F  (row vector times matrix)
+ *   The generalised coordinates are the n rows s_i = r_i F^-T followed by the three rows of n F, their velocities vel[n,3] and
+ *   vel_cell[3,3], their forces g_i and the rows of G.  Over these n + 3 rows exactly the step of snet_fire_step:
+ *     fm = largest row norm of the forces; fmax_sys[s] = fm; if fm < fmax: active = 0, status = 1, nothing else changes
+ *     P, |g|, |v| over all rows -> the velocity mixing and the dt / alpha / n_pos bookkeeping;  v += dt g;  dq = dt v, scaled to
+ *     length max_step if longer (norm over all rows)
+ *   move:  s_i += dq_i;  F_new = F + dQ / n (dQ the cell rows of dq);  C_new = C0 F_new^T;  r_i = s_i F_new^T;  n_steps += 1
+ *   guard, before anything but fmax_sys is written:  if the step length or an entry of F_new is not finite, det F_new <= 0, or a
+ *   face-to-face height of C_new is below min_height (the batched neighbour kernels take heights down to cutoff / 64):
+ *   active = 0, status = 2, and pos, cell, both velocities, dt, alpha, n_pos, n_steps keep their bits.
+ * Systems with active == 0 are not touched.  *n_active (device int32) receives the number of systems still active.
+ * One 256-thread workgroup per system, fp64 sums in a fixed order: two runs give identical bits.  Calls on one device must follow
+ * each other in stream order (the arrival word is apart from snet_fire_step's).  */
+int snet_fire_cell_step(double *pos, double *vel, double *cell, double *vel_cell, const double *cell0, const float *forces,
+                        const double *forces_extra, const double *virial, const double *virial_extra, int64_t n_atoms,
+                        const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos, int32_t *active,
+                        int32_t *n_steps, int32_t *status, double *fmax_sys, int32_t *n_active, double fmax, double dt_start,
+                        double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step,
+                        double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain, int32_t constant_volume,
+                        double min_height, void *stream);
+
 /* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
  * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
  * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of

@@ -133,6 +133,10 @@ SIGNATURES = {
     'snet_fire_step': (C.c_int, [c_f64p, c_f64p, c_f32p, c_f64p, C.c_int64, c_i32p, C.c_int32, c_f64p, c_f64p, c_i32p, c_i32p, c_i32p,
                                  c_f64p, c_i32p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_double, c_stream]),
+    'snet_fire_cell_step': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, C.c_int32,
+                                      c_f64p, c_f64p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p, C.c_double, C.c_double,
+                                      C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_double, c_stream]),
     'snet_mdb_step': (C.c_int, [c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, c_i32p, c_f64p,
                                 C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int32, c_stream]),
     'snet_mdb_init_velocities': (C.c_int, [c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, C.c_uint64, C.c_int32,

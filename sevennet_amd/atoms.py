@@ -57,10 +57,13 @@ class ManyAtomsMixin:
 
     def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
         """`relax_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc / set_positions): the
-        relaxed positions are written back with `set_positions`"""
+        relaxed positions are written back with `set_positions`; with relax_cell=True the relaxed cell first, with
+        `set_cell(cell, scale_atoms=False)`"""
         atoms_list = list(atoms_list)
         results = self.relax_many(*atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
         for a, r in zip(atoms_list, results):
+            if kw.get('relax_cell'):
+                a.set_cell(r['cell'], scale_atoms=False)
             a.set_positions(r['positions'])
         return results
 

@@ -131,14 +131,19 @@ def validate_batch_inputs(types, positions, cells, pbcs, cutoff: float, num_spec
 
 
 def _batched_neighbors(pos: torch.Tensor, atom_ptr: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, cutoff: float, dev,
-                       with_shifts: bool, extra_check: Optional[torch.Tensor] = None):
+                       with_shifts: bool, extra_check: Optional[torch.Tensor] = None, cells_dev: Optional[torch.Tensor] = None):
     """(row_ptr, src, center, edge_vec, shifts) of the systems [atom_ptr[b], atom_ptr[b+1]) of pos (device fp64): one count
-    launch, one scan, one fill launch and one device->host sync (the edge total; `extra_check`, a device flag, rides along)"""
+    launch, one scan, one fill launch and one device->host sync (the edge total; `extra_check`, a device flag, rides along).
+    cells_dev (fp64 [B,9] on the device): the cells the kernels read, instead of an upload of the host `cells`"""
     lib = _lib.load()
     n, B = int(pos.shape[0]), len(atom_ptr) - 1
     st, P = _lib.stream(), _lib.ptr
     ap = torch.as_tensor(atom_ptr.astype(np.int32)).to(dev)
-    cd = torch.as_tensor(np.ascontiguousarray(cells.reshape(B, 9))).to(dev)
+    if cells_dev is None:
+        cd = torch.as_tensor(np.ascontiguousarray(cells.reshape(B, 9))).to(dev)
+    else:
+        _lib.check_device_tensors('build_batch_graph (cells_dev)', pos, [(cells_dev, torch.float64, (B, 9))])
+        cd = cells_dev
     pd = torch.as_tensor(pbcs.astype(np.int32)).to(dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
     _lib.check(lib.snet_batch_nl_count(P(pos), P(ap), B, P(cd), P(pd), n, float(cutoff), P(count), st), 'snet_batch_nl_count')
@@ -239,7 +244,7 @@ def _fallback_graph(types_s, pos_s, cell, pbc, cutoff, dev, with_shifts: bool) -
 
 def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species: int, *, n_atoms=None, device='cuda:0',
                       species_rows: bool = False, with_shifts: bool = False, share_pairs: bool = True,
-                      max_atoms: int = BATCH_MAX_ATOMS) -> Graph:
+                      max_atoms: int = BATCH_MAX_ATOMS, cells_dev: Optional[torch.Tensor] = None) -> Graph:
     """A batch Graph of B systems for HipForceEngine.compute.
 
     types / positions: per-system sequences (species indices [n_s], positions [n_s,3] in Angstrom), or flat arrays
@@ -247,6 +252,8 @@ def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species:
     (row vectors) and pbcs[B,3] (or one [3] for all) are small metadata read on the host.  num_species: the model's species
     count (types outside [0, num_species) raise); species_rows: build the per-species row lists an FCTP self-connection
     reads.  Atoms keep the caller's order, so system b is rows [seg_ptr_host[b], seg_ptr_host[b+1]).
+    cells_dev: optional fp64 [B,9] tensor on the device with the cells the neighbor kernels read (a cell that moves on the
+    device, relax.fire_cell_loop); the host `cells` then only route the systems, all of which must take the batched kernel.
     Raises ValueError on empty systems, mismatched counts, unknown species and singular cells."""
     types, positions, n_at, cells, pbcs = _normalize(types, positions, cells, pbcs, n_atoms)
     dev = torch.device(device)
@@ -262,12 +269,16 @@ def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species:
                              f'(the model has {num_species})')
         ty = torch.as_tensor(types.astype(np.int32)).to(dev)
     kind = classify_systems(n_at, cells, pbcs, cutoff, max_atoms)
+    if cells_dev is not None and (kind != 0).any():
+        b = int(np.nonzero(kind != 0)[0][0])
+        raise ValueError(f'system {b}: cells on the device are read by the batched neighbor kernel only, which does not take this '
+                         f'system ({"more than " + str(max_atoms) + " atoms" if kind[b] == 1 else "a periodic height below cutoff / 64"})')
     with torch.cuda.device(dev):
         pos = positions.to(dev, torch.float64).contiguous() if isinstance(positions, torch.Tensor) \
             else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)
         fast = np.nonzero(kind == 0)[0]
         if len(fast) == B:   # every system in the batched kernel: the graph IS its output
-            row_ptr, src, center, ev, shifts, E = _batched_neighbors(pos, a_ptr, cells, pbcs, cutoff, dev, with_shifts, bad_types)
+            row_ptr, src, center, ev, shifts, E = _batched_neighbors(pos, a_ptr, cells, pbcs, cutoff, dev, with_shifts, bad_types, cells_dev)
             return _complete(_raw_graph(ty, row_ptr, center, src, ev, shifts, E), a_ptr, num_species if species_rows else 0, share_pairs)
         if bad_types is not None and bool(bad_types):
             raise ValueError('unknown species index in types')
@@ -306,9 +317,11 @@ class BatchForces:
         self.system_steps_evaluated = 0   # systems in the batch, summed over the engine calls
         self._ids = self._ty = None       # the systems whose species indices are on the device, and those indices
 
-    def __call__(self, pos: torch.Tensor, ids=None, want_atomic_virial: bool = False, with_extra: bool = True):
+    def __call__(self, pos: torch.Tensor, ids=None, want_atomic_virial: bool = False, with_extra: bool = True,
+                 cells_dev: Optional[torch.Tensor] = None):
         """Evaluate the systems `ids` (default: all, in the caller's order) at their flat device positions `pos` -> (graph,
-        the engine's output, extra forces fp64 [N,3] contiguous on the device or None, extra energies fp64 [b] or None)"""
+        the engine's output, extra forces fp64 [N,3] contiguous on the device or None, extra energies fp64 [b] or None).
+        cells_dev: the current cells of those systems (fp64 [b,9] on the device) where they are not the constructor's"""
         eng = self.engine
         dev = eng.dev
         ids = np.arange(len(self.n_atoms)) if ids is None else np.asarray(ids, np.int64)
@@ -316,7 +329,7 @@ class BatchForces:
             rows = np.concatenate([np.arange(self.a_ptr[b], self.a_ptr[b + 1]) for b in ids])
             self._ids, self._ty = ids.copy(), torch.as_tensor(self.types[rows].astype(np.int32)).to(dev)
         g = build_batch_graph(self._ty, pos, self.cells[ids], self.pbcs[ids], self.cutoff, eng.spec.num_species,
-                              n_atoms=self.n_atoms[ids], device=dev, species_rows=eng.needs_species_rows)
+                              n_atoms=self.n_atoms[ids], device=dev, species_rows=eng.needs_species_rows, cells_dev=cells_dev)
         out = eng.compute(g, want_atomic_virial=want_atomic_virial)
         self.n_force_calls += 1
         self.system_steps_evaluated += len(ids)

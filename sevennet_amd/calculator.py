@@ -288,7 +288,9 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         return batch_results(g, out, cells, self.compute_atomic_virial)
 
     def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
-        """Fixed-cell FIRE relaxation of B structures at once (sevennet_amd.relax.relax_batch): positions, velocities and the
+        """FIRE relaxation of B structures at once (sevennet_amd.relax.relax_batch), at fixed cells or, with relax_cell=True,
+        of the cells too (ASE's UnitCellFilter rule; further kw: scalar_pressure in eV/A^3, cell_mask, hydrostatic_strain,
+        constant_volume; the dicts then gain `cell` [3,3] and `status`: 'converged', 'steps' or 'cell_failed').  Positions, velocities and the
         optimizer state stay on the GPU from the first step to the last, converged systems stop moving at once and leave the
         batch when enough have finished.  One dict per system, in the given order: the keys of `compute` (evaluated at the
         returned positions) plus `positions` [n,3] fp64, `converged` (largest atomic force below fmax, eV/A) and `n_steps`.

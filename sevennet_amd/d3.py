@@ -266,7 +266,11 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         system with the keys of `compute` plus `positions`, `converged` and `n_steps`; the results are `compute_many` at the
         returned positions, the counters are kept as `self.relax_info`.  `D3Engine.compute_many` prepares its batch on the
         host, so this path copies the positions down and the D3 forces up once per step (the model's forces and the
-        optimizer state stay on the device)."""
+        optimizer state stay on the device).  Fixed cells only: relax_cell=True raises ValueError, because the D3 term reaches
+        the optimizer through the `extra` contract, which carries no virial."""
+        if kw.get('relax_cell'):
+            raise ValueError('relax_cell is not available with D3: the D3 term reaches the optimizer through the `extra` contract, '
+                             'which carries forces and energies but no virial, so its cell force is unknown')
         snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), list(positions_list)
         term = self._d3_term(numbers_list, positions_list, cells, pbcs)
