@@ -701,7 +701,21 @@ int snet_md_compute(snet_md_host *host, int32_t inum, const int32_t *ilist, cons
  * three launches, with the tables and settings of the handle (snet_d3_set_atoms / _set_cell are not used).  Every system's
  * results equal those of snet_d3_compute on it bit for bit.  Outputs are caller-owned host buffers: energy[n_sys] (eV),
  * forces[3 N] (eV/A), stress[9 n_sys] (as snet_d3_stress, per system), cn[N].  Errors name the system ("system 3: ...");
- * at most 2^31 - 1 atoms in total.  Synchronises `stream` before it returns.                                           */
+ * at most 2^31 - 1 atoms in total.  Synchronises `stream` before it returns.
+ * Device-resident evaluation (the D3 term of the batched drivers): snet_d3_plan does ONCE per set of systems the host work that
+ * depends on species and topology only (dense type index, per-atom rcov / r2r4, the r0 and reference-C6 slices, atom ranges) and
+ * fixes a translation CAPACITY per system and list: the count of lattice translations with every periodic axis' repetition
+ * count one larger than for the plan's cell (cells_move != 0), exactly that of the plan's cell (cells_move == 0), 27 for a system
+ * with box_rule[s] != 0 (the molecule box of sevenn/calculator.py:533-548, formed from the positions of each call, pbc all
+ * true).  All device memory is allocated there; a plan whose translation storage would exceed 2^27 doubles is refused.  A handle
+ * holds one plan; planning again replaces it.  Synchronises `stream`.
+ * snet_d3_compute_device evaluates the planned systems at DEVICE positions[N,3] (A) and DEVICE cells[n_sys,9] (A; NULL: the
+ * plan's) into device outputs: energy[n_sys] (eV), forces[N,3] (eV/A), virial[n_sys,6] in the engine's convention (order
+ * xx,yy,zz,xy,yz,zx, stress = -virial / volume: what snet_fire_cell_step takes as virial_extra), and, each nullable, cn[N],
+ * volume[n_sys] (A^3), status[n_sys].  Six launches on `stream`, no host read, no synchronisation, no allocation; the work is
+ * bounded by the plan's capacities whatever the cells hold.  status 1: the system's cell is not finite, |det| <= 1e-12 bohr^3, or
+ * a translation list would exceed its capacity -- its energy, forces and virial are NaN, every other system is unaffected.
+ * Energy, forces and cn equal snet_d3_compute_batch on the same inputs bit for bit.                                        */
 typedef struct snet_d3 snet_d3;
 int snet_d3_create(snet_d3 **out);
 void snet_d3_destroy(snet_d3 *d3);
@@ -714,6 +728,12 @@ int snet_d3_compute_batch(snet_d3 *d3, int32_t n_sys, const int64_t *atom_ptr /*
                           const double *positions /*[N*3], A*/, const double *cells /*[n_sys*9], A*/, const int32_t *pbc /*[n_sys*3]*/,
                           double *energy /*[n_sys], eV*/, double *forces /*[N*3], eV/A*/, double *stress /*[n_sys*9], eV/A^3*/,
                           double *cn /*[N]*/, void *stream);
+int snet_d3_plan(snet_d3 *d3, int32_t n_sys, const int64_t *atom_ptr /*[n_sys+1]*/, const int32_t *atomic_numbers /*[N]*/,
+                 const double *cells /*[n_sys*9], A*/, const int32_t *pbc /*[n_sys*3]*/, const int32_t *box_rule /*[n_sys]*/,
+                 int32_t cells_move, void *stream);
+int snet_d3_compute_device(snet_d3 *d3, const double *positions /*[N*3], A, device*/, const double *cells /*[n_sys*9], A, device*/,
+                           double *energy /*[n_sys]*/, double *forces /*[N*3]*/, double *virial /*[n_sys*6]*/, double *cn /*[N]*/,
+                           double *volume /*[n_sys]*/, int32_t *status /*[n_sys]*/, void *stream);
 double snet_d3_energy(const snet_d3 *d3);
 const double *snet_d3_forces(const snet_d3 *d3);
 const double *snet_d3_stress(const snet_d3 *d3);

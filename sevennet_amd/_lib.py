@@ -196,6 +196,8 @@ SIGNATURES = {
     'snet_d3_compute': (C.c_int, [C.c_void_p, c_stream]),
     'snet_d3_compute_batch': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream]),
+    'snet_d3_plan': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, c_stream]),
+    'snet_d3_compute_device': (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_stream]),
     'snet_d3_energy': (C.c_double, [C.c_void_p]),
     'snet_d3_forces': (C.POINTER(C.c_double), [C.c_void_p]),
     'snet_d3_stress': (C.POINTER(C.c_double), [C.c_void_p]),

@@ -306,7 +306,10 @@ class BatchForces:
     engine: a HipForceEngine; types int64 [N] on the host, n_atoms [B], cells [B,3,3], pbcs [B,3] as `validate_batch_inputs`
     returns them.  extra: optional callable (positions fp64 [N,3] on the device, seg_ptr int64 [b+1] on the host, ids int64
     [b]: the caller's index of each system of the current batch) -> forces [N,3], or (forces, energy_per_system [b]); numpy or
-    torch, on any device.  Nothing touches the device before the first evaluation."""
+    torch, on any device.  An `extra` with the attribute `provides_virial = True` (d3.D3DeviceTerm) is also passed
+    `cells_dev=` and may return (forces, energies, virial [b,6] in the engine's convention: order xx,yy,zz,xy,yz,zx, stress =
+    -virial / volume); the virial of the last evaluation is kept as `virial_extra` (None where there is none), which is where
+    relax.fire_cell_loop picks it up.  Nothing touches the device before the first evaluation."""
 
     def __init__(self, engine, types: np.ndarray, n_atoms: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, cutoff: float,
                  extra: Optional[Callable] = None):
@@ -316,6 +319,7 @@ class BatchForces:
         self.n_force_calls = 0            # engine calls
         self.system_steps_evaluated = 0   # systems in the batch, summed over the engine calls
         self._ids = self._ty = None       # the systems whose species indices are on the device, and those indices
+        self.virial_extra = None          # fp64 [b,6] on the device: the virial of `extra` at the last evaluation, if it gave one
 
     def __call__(self, pos: torch.Tensor, ids=None, want_atomic_virial: bool = False, with_extra: bool = True,
                  cells_dev: Optional[torch.Tensor] = None):
@@ -333,11 +337,16 @@ class BatchForces:
         out = eng.compute(g, want_atomic_virial=want_atomic_virial)
         self.n_force_calls += 1
         self.system_steps_evaluated += len(ids)
-        fx = ex = None
+        fx = ex = self.virial_extra = None
         if self.extra is not None and with_extra:
-            fx = self.extra(pos, g.seg_ptr_host, ids)
+            if getattr(self.extra, 'provides_virial', False):
+                fx = self.extra(pos, g.seg_ptr_host, ids, cells_dev=cells_dev)
+            else:
+                fx = self.extra(pos, g.seg_ptr_host, ids)
             if isinstance(fx, tuple):
-                fx, ex = fx
+                if len(fx) == 3:
+                    self.virial_extra = torch.as_tensor(fx[2]).to(dev, torch.float64).reshape(len(ids), 6).contiguous()
+                fx, ex = fx[:2]
                 ex = torch.as_tensor(ex).to(dev, torch.float64).reshape(len(ids))
             fx = torch.as_tensor(fx).to(dev, torch.float64).contiguous()
         return g, out, fx, ex

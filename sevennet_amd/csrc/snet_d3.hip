@@ -214,6 +214,187 @@ __global__ __launch_bounds__(NTH) void d3_cn_force_kernel(const D3Sys *__restric
   }
 }
 
+// ---- device-resident evaluation (snet_d3_plan / snet_d3_compute_device): what d3_run does on the host per call -- the molecule
+// box, the cell in bohr with its inverse, both translation lists, the wrap, the per-system sums -- as four small kernels around
+// the three above.  They are plain IEEE fp64 with the operations of the host code in its order, and floating-point contraction
+// is switched off in each (the x86 host build has no fused multiply-add to contract into), so they reproduce the host's bits.
+
+// what the plan fixes per system: the atom range, the slots and capacities of its two translation lists, the box rule
+struct D3PlanSys {
+  int64_t a0, tv0, tc0;
+  int32_t n, cap_v, cap_c, box, pbc[3], pad;
+  double cell[9];   // the plan's cell (A): read where the call passes no cells
+};
+// what d3_prepare_kernel derives per system and call: the cell in bohr, its inverse, the volume (A^3), the status word
+struct D3Geo {
+  double a[9], inv[9], vol;
+  int32_t status, pad;
+};
+
+// repetition counts of `translations` below for one cutoff radius rc: |n_k| <= int(rc / height_k) + 1 along periodic axes.
+// false: a count that is not finite or beyond 1e5 (a cell that has collapsed along that axis)
+__host__ __device__ inline bool d3_reps(const double *a, const int32_t *pbc, double rc, int rep[3]) {
+#pragma clang fp contract(off)
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double *u = a + 3 * ((k + 1) % 3), *v = a + 3 * ((k + 2) % 3), *w = a + 3 * k;
+    const double cp[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+    const double h = fabs((cp[0] * w[0] + cp[1] * w[1] + cp[2] * w[2]) / sqrt(cp[0] * cp[0] + cp[1] * cp[1] + cp[2] * cp[2]));
+    rep[k] = 0;
+    if (pbc[k]) {
+      const double q = fabs(rc / h);
+      if (q < 1e5) rep[k] = (int)q + 1;   // (a NaN fails the comparison)
+      else ok = false;
+    }
+  }
+  return ok;
+}
+__host__ __device__ inline int64_t d3_rep_count(const int rep[3]) {
+  return (int64_t)(2 * rep[0] + 1) * (2 * rep[1] + 1) * (2 * rep[2] + 1);
+}
+
+// translation t of the (p, q, r) loop nest of `translations` below, into tau[3 t ..]
+__device__ __forceinline__ void d3_put_translation(const double *a, const int rep[3], int64_t t, double *tau) {
+#pragma clang fp contract(off)
+  const int n1 = 2 * rep[1] + 1, n2 = 2 * rep[2] + 1;
+  const int r = (int)(t % n2) - rep[2], q = (int)((t / n2) % n1) - rep[1], p = (int)(t / ((int64_t)n1 * n2)) - rep[0];
+  for (int c = 0; c < 3; ++c) tau[3 * t + c] = p * a[c] + q * a[3 + c] + r * a[6 + c];
+}
+
+// one workgroup per system: its cell (the molecule box from the positions' extent where the plan says so), D3Geo, both
+// translation lists into the system's slots, D3Sys.  A system whose cell is not finite or singular, or whose lists would not
+// fit their capacity, gets status 1 and empty lists: the three kernels above then loop over nothing for its atoms.
+__global__ __launch_bounds__(NTH) void d3_prepare_kernel(const D3PlanSys *__restrict__ plan, const double *__restrict__ pos,
+                                                         const double *__restrict__ cells, double box_pad, double rc_v, double rc_c,
+                                                         D3Sys *__restrict__ sys, D3Geo *__restrict__ geo, double *__restrict__ tv,
+                                                         double *__restrict__ tc) {
+#pragma clang fp contract(off)
+  __shared__ double sh[NTH / 64][6];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const D3PlanSys P = plan[s];
+  double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t pbc[3] = {1, 1, 1};
+  if (P.box) {   // (uniform over the workgroup) extent + box_pad + 1 A along each axis, periodic
+    double m[6] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};   // min x,y,z | min of -x,-y,-z
+    for (int i = tid; i < P.n; i += NTH)
+      for (int k = 0; k < 3; ++k) {
+        const double v = pos[3 * (P.a0 + i) + k];
+        m[k] = fmin(m[k], v);
+        m[3 + k] = fmin(m[3 + k], -v);
+      }
+    for (int k = 0; k < 6; ++k) {
+      for (int o = 32; o > 0; o >>= 1) m[k] = fmin(m[k], __shfl_xor(m[k], o, 64));
+      if ((tid & 63) == 0) sh[tid >> 6][k] = m[k];
+    }
+    __syncthreads();
+    for (int k = 0; k < 3; ++k) {
+      const double lo = fmin(fmin(sh[0][k], sh[1][k]), fmin(sh[2][k], sh[3][k]));
+      const double hi = -fmin(fmin(sh[0][3 + k], sh[1][3 + k]), fmin(sh[2][3 + k], sh[3][3 + k]));
+      c[4 * k] = hi - lo + box_pad + 1.0;
+    }
+  } else {
+    const double *src = cells ? cells + 9 * (int64_t)s : P.cell;
+    for (int k = 0; k < 9; ++k) c[k] = src[k];
+    for (int k = 0; k < 3; ++k) pbc[k] = P.pbc[k];
+  }
+  D3Geo G;
+  double *a = G.a;
+  bool ok = true;
+  for (int k = 0; k < 9; ++k) {
+    a[k] = c[k] / AU_TO_ANG;
+    ok = ok && (a[k] - a[k] == 0.0);
+  }
+  const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+  ok = ok && fabs(det) > 1e-12;
+  const double inv[9] = {(a[4] * a[8] - a[5] * a[7]) / det, (a[2] * a[7] - a[1] * a[8]) / det, (a[1] * a[5] - a[2] * a[4]) / det,
+                         (a[5] * a[6] - a[3] * a[8]) / det, (a[0] * a[8] - a[2] * a[6]) / det, (a[2] * a[3] - a[0] * a[5]) / det,
+                         (a[3] * a[7] - a[4] * a[6]) / det, (a[1] * a[6] - a[0] * a[7]) / det, (a[0] * a[4] - a[1] * a[3]) / det};
+  for (int k = 0; k < 9; ++k) G.inv[k] = inv[k];
+  G.vol = fabs(det) * AU_TO_ANG * AU_TO_ANG * AU_TO_ANG;
+  int rv[3], rc[3];
+  ok = d3_reps(a, pbc, rc_v, rv) && ok;
+  ok = d3_reps(a, pbc, rc_c, rc) && ok;
+  int64_t Tv = 0, Tc = 0;
+  if (ok) {
+    Tv = d3_rep_count(rv);
+    Tc = d3_rep_count(rc);
+    ok = Tv <= P.cap_v && Tc <= P.cap_c;
+  }
+  if (!ok) Tv = Tc = 0;
+  for (int64_t t = tid; t < Tv; t += NTH) d3_put_translation(a, rv, t, tv + 3 * P.tv0);
+  for (int64_t t = tid; t < Tc; t += NTH) d3_put_translation(a, rc, t, tc + 3 * P.tc0);
+  if (tid == 0) {
+    D3Sys S;
+    S.a0 = P.a0, S.tv0 = P.tv0, S.tc0 = P.tc0, S.n = P.n;
+    S.Tv = (int32_t)Tv, S.Tc = (int32_t)Tc;
+    S.zv = ok ? (rv[0] * (2 * rv[1] + 1) + rv[1]) * (2 * rv[2] + 1) + rv[2] : 0;
+    S.zc = ok ? (rc[0] * (2 * rc[1] + 1) + rc[1]) * (2 * rc[2] + 1) + rc[2] : 0;
+    const int64_t want = (4 * NTH + (int64_t)P.n - 1) / P.n;   // >= 4 work items per thread where the images allow it (d3_run)
+    const int64_t have = Tv < want ? Tv : want;
+    S.t_chunks = (int32_t)(have > 1 ? have : 1);
+    sys[s] = S;
+    G.status = ok ? 0 : 1;
+    G.pad = 0;
+    geo[s] = G;
+  }
+}
+
+// one thread per atom: the position in bohr wrapped into its system's cell (d3_run's loop; load_atom_info, :1170-1219)
+__global__ __launch_bounds__(NTH) void d3_wrap_kernel(const int32_t *__restrict__ sys_of, const D3Geo *__restrict__ geo,
+                                                      const double *__restrict__ pos, int n_atoms, double *__restrict__ x) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * NTH + threadIdx.x;
+  if (i >= n_atoms) return;
+  const D3Geo *G = geo + sys_of[i];
+  const double *p = pos + 3 * i, *a = G->a, *inv = G->inv;
+  if (G->status != 0) {   // (nothing reads a flagged system's coordinates: its lists are empty)
+    x[3 * i] = x[3 * i + 1] = x[3 * i + 2] = 0.0;
+    return;
+  }
+  double fr[3];
+  for (int c = 0; c < 3; ++c) {
+    fr[c] = 0.0;
+    for (int k = 0; k < 3; ++k) fr[c] += p[k] / AU_TO_ANG * inv[3 * k + c];
+    fr[c] -= floor(fr[c]);
+  }
+  for (int c = 0; c < 3; ++c) x[3 * i + c] = fr[0] * a[c] + fr[1] * a[3 + c] + fr[2] * a[6 + c];
+}
+
+// one workgroup per system: the energy and the six strain shares summed sequentially in atom order (one thread per sum, as the
+// host loop of d3_run), scaled to eV; the virial in the engine's convention (xx,yy,zz,xy,yz,zx; stress = -virial / V) from the
+// strain derivative in this file's order (xx,yy,zz,xy,xz,yz); the forces scaled to eV/A.  NaN for a flagged system.
+__global__ __launch_bounds__(NTH) void d3_reduce_kernel(const D3Sys *__restrict__ sys, const D3Geo *__restrict__ geo,
+                                                        const double *__restrict__ e_atom, const double *__restrict__ s_atom,
+                                                        const double *__restrict__ f, const double *__restrict__ cn,
+                                                        double *__restrict__ energy, double *__restrict__ forces,
+                                                        double *__restrict__ virial, double *__restrict__ cn_out,
+                                                        double *__restrict__ volume, int32_t *__restrict__ status) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const D3Sys S = sys[s];
+  const bool bad = geo[s].status != 0;
+  if (tid < 7) {
+    const double *src = tid == 0 ? e_atom + S.a0 : s_atom + 6 * S.a0 + (tid - 1);
+    const int stride = tid == 0 ? 1 : 6;
+    double acc = 0.0;
+    for (int i = 0; i < S.n; ++i) acc += src[(int64_t)i * stride];
+    if (tid == 0) {
+      energy[s] = bad ? NAN : acc * AU_TO_EV;
+    } else {
+      const int slot[6] = {0, 1, 2, 3, 5, 4};   // xx,yy,zz,xy,xz,yz -> xx,yy,zz,xy,yz,zx
+      virial[6 * (int64_t)s + slot[tid - 1]] = bad ? NAN : -(acc * AU_TO_EV);
+    }
+  }
+  for (int k = tid; k < 3 * S.n; k += NTH) forces[3 * S.a0 + k] = bad ? NAN : f[3 * S.a0 + k] * (AU_TO_EV / AU_TO_ANG);
+  if (cn_out)
+    for (int k = tid; k < S.n; k += NTH) cn_out[S.a0 + k] = cn[S.a0 + k];
+  if (tid == 0) {
+    if (volume) volume[s] = geo[s].vol;
+    if (status) status[s] = geo[s].status;
+  }
+}
+
 template <class T>
 struct Dev {
   T *p = nullptr;
@@ -256,6 +437,19 @@ struct snet_d3 {
   Dev<double> d_in, d_work;
   Dev<int32_t> d_int;
   Dev<D3Sys> d_sys;
+  // the plan of snet_d3_plan, with device buffers of its own (snet_d3_compute(_batch) between two planned calls disturbs nothing):
+  // p_x = x [3N] | tv [3 cap_v] | tc [3 cap_c], written by the kernels of each call; p_tab = rcov [N] | r2r4 [N] | r0 [nt nt] |
+  // ref [nt nt 5 5 3] and p_int = type [N] | sys_of [N] | mxc [nt], uploaded once; p_work as d_work
+  struct Plan {
+    bool ready = false;
+    int32_t B = 0, N = 0, nt = 0;
+    int64_t cap_v = 0, cap_c = 0;
+    Dev<double> p_x, p_tab, p_work;
+    Dev<int32_t> p_int;
+    Dev<D3PlanSys> p_plan;
+    Dev<D3Sys> p_sys;
+    Dev<D3Geo> p_geo;
+  } plan;
 };
 
 extern "C" {
@@ -287,6 +481,7 @@ int snet_d3_set_tables(snet_d3 *d, const double *r0ab, const double *c6ab, int64
     d->mxc[zj] = std::max(d->mxc[zj], rj + 1);
   }
   d->have_tables = true;
+  d->plan.ready = false;   // (a plan holds slices of the tables)
   return 0;
 }
 
@@ -300,6 +495,7 @@ int snet_d3_settings(snet_d3 *d, double vdw_cutoff_au2, double cn_cutoff_au2, in
   // func5 = (s6, rs6, s18, rs18, alp) of the functional; a1 = rs6, a2 = rs8 = rs18, s8 = s18, alp8 = alp + 2 (:608-628)
   d->func = Func{func5[0], func5[1], func5[2], func5[3], func5[4], func5[4] + 2.0, damping};
   d->have_func = true;
+  d->plan.ready = false;   // (a plan's capacities come from the cutoffs)
   return 0;
 }
 
@@ -477,6 +673,113 @@ int snet_d3_compute_batch(snet_d3 *d, int32_t n_sys, const int64_t *atom_ptr, co
                "snet_d3_compute_batch: null argument");
   return d3_run(d, n_sys, atom_ptr, atomic_numbers, positions, cells, pbc, energy, forces, stress, cn, static_cast<hipStream_t>(stream),
                 "snet_d3_compute_batch", true);
+}
+
+int snet_d3_plan(snet_d3 *d, int32_t n_sys, const int64_t *atom_ptr, const int32_t *atomic_numbers, const double *cells,
+                 const int32_t *pbc, const int32_t *box_rule, int32_t cells_move, void *stream) {
+  const std::string who = "snet_d3_plan";
+  SNET_REQUIRE(d && atom_ptr && atomic_numbers && cells && pbc && box_rule, who + ": null argument");
+  SNET_REQUIRE(d->have_tables && d->have_func, who + ": tables and settings must be set first");
+  SNET_REQUIRE(n_sys >= 1 && atom_ptr[0] == 0, who + ": need n_sys >= 1 and atom_ptr[0] == 0");
+  auto sys_msg = [&](int s, const std::string &m) { return who + ": system " + std::to_string(s) + ": " + m; };
+  for (int s = 0; s < n_sys; ++s) SNET_REQUIRE(atom_ptr[s + 1] > atom_ptr[s], sys_msg(s, "no atoms (atom_ptr must increase)"));
+  SNET_REQUIRE(atom_ptr[n_sys] <= (int64_t)INT32_MAX, who + ": more than 2^31 - 1 atoms in total");
+  const int B = n_sys, N = (int)atom_ptr[B];
+  const int32_t *z = atomic_numbers;
+  auto &P = d->plan;
+  P.ready = false;
+  std::vector<D3PlanSys> ps(B);
+  std::vector<int32_t> ints(2 * (size_t)N);   // type [N] | sys_of [N] | mxc [nt] (appended below)
+  const double rc_v = std::sqrt(d->vdw_cut), rc_c = std::sqrt(d->cn_cut);
+  int64_t tot_v = 0, tot_c = 0;
+  for (int s = 0; s < B; ++s) {
+    D3PlanSys &S = ps[s];
+    S.a0 = atom_ptr[s];
+    S.n = (int32_t)(atom_ptr[s + 1] - S.a0);
+    S.box = box_rule[s] != 0;
+    S.pad = 0;
+    for (int64_t i = atom_ptr[s]; i < atom_ptr[s + 1]; ++i) {
+      SNET_REQUIRE(z[i] >= 1 && z[i] <= 94, sys_msg(s, "Z = " + std::to_string(z[i]) + ": D3 parameters exist for Z = 1 .. 94"));
+      ints[(size_t)N + i] = s;
+    }
+    for (int k = 0; k < 9; ++k) S.cell[k] = cells[9 * (size_t)s + k];
+    int64_t cv = 27, cc = 27;   // the molecule box is wider than both cutoffs: one image each way
+    for (int k = 0; k < 3; ++k) S.pbc[k] = S.box ? 1 : pbc[3 * s + k] != 0;
+    if (!S.box) {
+      double a[9];
+      for (int k = 0; k < 9; ++k) a[k] = S.cell[k] / AU_TO_ANG;
+      const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+      SNET_REQUIRE(std::fabs(det) > 1e-12, sys_msg(s, "singular cell (give molecules a box: the reference's calculator does, calculator.py:533-548)"));
+      int rv[3], rc[3];
+      SNET_REQUIRE(d3_reps(a, S.pbc, rc_v, rv) && d3_reps(a, S.pbc, rc_c, rc), sys_msg(s, "a periodic height of the cell is below cutoff / 1e5"));
+      if (cells_move)   // room for every periodic axis' repetition count to grow by one
+        for (int k = 0; k < 3; ++k) { rv[k] += S.pbc[k]; rc[k] += S.pbc[k]; }
+      cv = d3_rep_count(rv);
+      cc = d3_rep_count(rc);
+    }
+    S.tv0 = tot_v;
+    S.tc0 = tot_c;
+    tot_v += cv;
+    tot_c += cc;
+    SNET_REQUIRE(3 * (tot_v + tot_c) <= ((int64_t)1 << 27),
+                 sys_msg(s, "the translation lists up to this system need " + std::to_string(3 * (tot_v + tot_c)) +
+                                " doubles, more than the 2^27 a plan may hold (use fewer or larger cells per plan)"));
+    S.cap_v = (int32_t)cv;
+    S.cap_c = (int32_t)cc;
+  }
+  // elements present -> dense type index and their slices of the tables, as d3_run
+  std::vector<int> type_of(95, -1), elems;
+  for (int i = 0; i < N; ++i) {
+    if (type_of[z[i]] < 0) { type_of[z[i]] = (int)elems.size(); elems.push_back(z[i]); }
+    ints[i] = type_of[z[i]];
+  }
+  const int nt = (int)elems.size();
+  const size_t o_r2r4 = N, o_r0 = 2 * (size_t)N, o_ref = o_r0 + (size_t)nt * nt;
+  std::vector<double> tab(o_ref + (size_t)nt * nt * MAXREF * MAXREF * 3);
+  for (int i = 0; i < N; ++i) { tab[i] = d->rcov[z[i] - 1]; tab[o_r2r4 + i] = d->r2r4[z[i] - 1]; }
+  for (int p = 0; p < nt; ++p) {
+    ints.push_back(d->mxc[elems[p]]);
+    for (int q = 0; q < nt; ++q) {
+      std::memcpy(&tab[o_ref + ((size_t)p * nt + q) * MAXREF * MAXREF * 3], &d->c6ref[((size_t)elems[p] * 95 + elems[q]) * MAXREF * MAXREF * 3],
+                  sizeof(double) * MAXREF * MAXREF * 3);
+      tab[o_r0 + (size_t)p * nt + q] = d->r0ab[(size_t)(elems[p] - 1) * 94 + elems[q] - 1] / AU_TO_ANG;
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // (the uploads read host vectors that die with this call: wait for them)
+  const bool ok = P.p_tab.put(tab, st) && P.p_int.put(ints, st) && P.p_plan.put(ps, st) && P.p_sys.ensure(B) && P.p_geo.ensure(B) &&
+                  P.p_x.ensure(3 * ((size_t)N + tot_v + tot_c)) && P.p_work.ensure(12 * (size_t)N) &&
+                  hipStreamSynchronize(st) == hipSuccess;
+  SNET_REQUIRE(ok, who + ": device allocation / upload failed");
+  P.B = B, P.N = N, P.nt = nt, P.cap_v = tot_v, P.cap_c = tot_c;
+  P.ready = true;
+  return 0;
+}
+
+int snet_d3_compute_device(snet_d3 *d, const double *positions, const double *cells, double *energy, double *forces, double *virial,
+                           double *cn, double *volume, int32_t *status, void *stream) {
+  SNET_REQUIRE(d && positions && energy && forces && virial, "snet_d3_compute_device: null argument");
+  SNET_REQUIRE(d->plan.ready, "snet_d3_compute_device: no plan (snet_d3_plan first, and again after new tables or settings)");
+  auto &P = d->plan;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t N = P.N;
+  double *X = P.p_x.p, *TV = X + 3 * N, *TC = TV + 3 * P.cap_v;
+  const double *RCOV = P.p_tab.p, *R2R4 = RCOV + N, *R0 = R2R4 + N, *REF = R0 + (size_t)P.nt * P.nt;
+  const int32_t *TYPE = P.p_int.p, *SYS_OF = TYPE + N, *MXC = SYS_OF + N;
+  // work array as d3_run: e [N] | s [6N] | f [3N] | cn [N] | dE/dCN [N]
+  double *W = P.p_work.p;
+  const size_t o_s = N, o_f = 7 * N, o_cn = 10 * N, o_dc = 11 * N;
+  const double box_pad = std::sqrt(std::max(d->vdw_cut, d->cn_cut)) * AU_TO_ANG;
+  d3_prepare_kernel<<<P.B, NTH, 0, st>>>(P.p_plan.p, positions, cells, box_pad, std::sqrt(d->vdw_cut), std::sqrt(d->cn_cut), P.p_sys.p,
+                                         P.p_geo.p, TV, TC);
+  d3_wrap_kernel<<<(P.N + NTH - 1) / NTH, NTH, 0, st>>>(SYS_OF, P.p_geo.p, positions, P.N, X);
+  d3_cn_kernel<<<P.N, NTH, 0, st>>>(P.p_sys.p, SYS_OF, X, TC, RCOV, d->cn_cut, W + o_cn);
+  d3_pair_kernel<<<P.N, NTH, 0, st>>>(P.p_sys.p, SYS_OF, X, TV, R2R4, R0, TYPE, P.nt, W + o_cn, MXC, REF, d->vdw_cut, d->func, W,
+                                      W + o_f, W + o_dc, W + o_s);
+  d3_cn_force_kernel<<<P.N, NTH, 0, st>>>(P.p_sys.p, SYS_OF, X, TC, RCOV, d->cn_cut, W + o_dc, W + o_f, W + o_s);
+  d3_reduce_kernel<<<P.B, NTH, 0, st>>>(P.p_sys.p, P.p_geo.p, W, W + o_s, W + o_f, W + o_cn, energy, forces, virial, cn, volume, status);
+  SNET_CHECK_LAUNCH("snet_d3_compute_device");
+  return 0;
 }
 
 double snet_d3_energy(const snet_d3 *d) { return d ? d->energy : 0.0; }

@@ -73,6 +73,27 @@ def prepare_d3_batch(numbers, positions, cells, pbcs, rthr: float, cnthr: float,
     return D3Batch(atom_ptr, np.ascontiguousarray(numbers, np.int32), positions, cells_out, pbcs_out)
 
 
+class D3Plan(NamedTuple):
+    """a plan of `D3Engine.plan` and the device tensors `D3Engine.compute_device` writes (overwritten by each call)"""
+    atom_ptr: np.ndarray    # int64 [B+1], host
+    cells_move: bool        # capacities leave room for one more repetition along every periodic axis
+    energy: Any             # fp64 [B], eV
+    forces: Any             # fp64 [N,3], eV/A
+    virial: Any             # fp64 [B,6], the engine's convention (`stress_to_virial`)
+    cn: Any                 # fp64 [N]
+    volume: Any             # fp64 [B], A^3 (of the molecule box where that rule applies)
+    status: Any             # int32 [B]: 1 = cell not finite, singular, or more lattice translations than the plan has room for
+
+
+def stress_to_virial(stress, volume):
+    """[..., 6] virial in the engine's convention -- order xx,yy,zz,xy,yz,zx, stress = -virial / volume: what
+    `relax.fire_cell_step` adds to the model's `virial_per_system` -- from the D3 stress [..., 3, 3] (dE/d strain / volume,
+    eV/A^3) and the volume(s) (A^3)"""
+    s = np.asarray(stress, np.float64)
+    six = np.stack([s[..., 0, 0], s[..., 1, 1], s[..., 2, 2], s[..., 0, 1], s[..., 1, 2], s[..., 2, 0]], axis=-1)
+    return -six * np.asarray(volume, np.float64)[..., None]
+
+
 class D3Engine:
     """thin handle over snet_d3_*: compute(numbers, positions, cell, pbc) -> energy, forces, stress (3x3, dE/d strain / V)"""
 
@@ -128,6 +149,63 @@ class D3Engine:
         return [dict(energy=float(energy[b]), forces=forces[ap[b]:ap[b + 1]], stress=stress[b], cn=cn[ap[b]:ap[b + 1]])
                 for b in range(B)]
 
+    def plan(self, numbers, n_atoms, cells, pbcs, cells_move: bool = False, device=None) -> 'D3Plan':
+        """snet_d3_plan for B systems: numbers flat [N], n_atoms [B], cells [B,3,3] (A) and pbcs [B,3] (or one [3]) as the caller
+        has them -- a cell that sums to zero marks a molecule, whose box `compute_device` forms from the positions of each call.
+        Everything that depends on species and topology alone is prepared and uploaded here, once, and the capacity of each
+        system's translation lists is fixed: exact for its cell, or, with cells_move, with every periodic axis' repetition count
+        one larger.  -> the plan with its output tensors on `device` (default: the current GPU).  The engine holds ONE plan:
+        planning again makes the earlier plan unusable.  ValueError on an empty batch or system, Z outside 1..94 and a singular
+        cell."""
+        import torch
+        n_atoms = _as_host(n_atoms, np.int64).reshape(-1)
+        numbers = np.ascontiguousarray(_as_host(numbers, np.int64).reshape(-1))
+        B = len(n_atoms)
+        if B == 0 or (n_atoms <= 0).any() or int(n_atoms.sum()) != len(numbers):
+            raise ValueError(f'n_atoms {n_atoms.tolist()} (all positive) must sum to the {len(numbers)} atomic numbers')
+        atom_ptr = np.concatenate([[0], np.cumsum(n_atoms)]).astype(np.int64)
+        if atom_ptr[-1] > 2 ** 31 - 1:
+            raise ValueError(f'{int(atom_ptr[-1])} atoms: at most 2^31 - 1 in one D3 batch')
+        bad = (numbers < 1) | (numbers > 94)
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise ValueError(f'system {system_of(atom_ptr, i)}: Z = {int(numbers[i])} has no D3 parameters (Z = 1 .. 94)')
+        cells = np.ascontiguousarray(_as_host(cells, np.float64).reshape(B, 3, 3))
+        pbcs = np.ascontiguousarray(np.broadcast_to(_as_host(pbcs, bool).reshape(-1, 3), (B, 3)).astype(np.int32))
+        box = np.ascontiguousarray((cells.reshape(B, 9).sum(1) == 0).astype(np.int32))   # the rule of `molecule_box`
+        for b in np.nonzero(box == 0)[0]:
+            if not abs(np.linalg.det(cells[b] / AU_TO_ANG)) > 1e-12:
+                raise ValueError(f'system {b}: singular cell {cells[b].tolist()} (pbc {pbcs[b].astype(bool).tolist()})')
+        z32 = np.ascontiguousarray(numbers, np.int32)
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        with torch.cuda.device(dev):
+            _lib.check(self.lib.snet_d3_plan(self.handle, B, _dp(atom_ptr), _dp(z32), _dp(cells), _dp(pbcs), _dp(box),
+                                             int(bool(cells_move)), _lib.stream()), 'snet_d3_plan')
+            f64, N = torch.float64, int(atom_ptr[-1])
+            self._plan = D3Plan(atom_ptr, bool(cells_move), torch.empty(B, dtype=f64, device=dev), torch.empty(N, 3, dtype=f64, device=dev),
+                                torch.empty(B, 6, dtype=f64, device=dev), torch.empty(N, dtype=f64, device=dev),
+                                torch.empty(B, dtype=f64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+        return self._plan
+
+    def compute_device(self, plan: 'D3Plan', positions, cells_dev=None) -> 'D3Plan':
+        """snet_d3_compute_device on the current stream: the planned systems at `positions` (fp64 [N,3] on the plan's device,
+        A) and, where given, `cells_dev` (fp64 [B,9] on the device, A; None: the plan's cells) into the plan's output tensors,
+        which the next call overwrites.  Six launches; nothing is read back, nothing synchronises, nothing is allocated.
+        Energy, forces and cn equal `compute_many` on the same inputs bit for bit; a system with status 1 (see `D3Plan`) holds
+        NaN."""
+        import torch
+        if plan is not getattr(self, '_plan', None):
+            raise ValueError('this plan has been replaced: a D3Engine holds one plan at a time (plan again)')
+        B, N = len(plan.atom_ptr) - 1, int(plan.atom_ptr[-1])
+        want = [(positions, torch.float64, (N, 3))] + ([] if cells_dev is None else [(cells_dev, torch.float64, (B, 9))])
+        _lib.check_device_tensors('D3Engine.compute_device', plan.forces, want)
+        P = _lib.ptr
+        with torch.cuda.device(plan.forces.device):
+            _lib.check(self.lib.snet_d3_compute_device(self.handle, P(positions), P(cells_dev), P(plan.energy), P(plan.forces),
+                                                       P(plan.virial), P(plan.cn), P(plan.volume), P(plan.status), _lib.stream()),
+                       'snet_d3_compute_device')
+        return plan
+
     def __del__(self):
         try:
             if getattr(self, 'handle', None):
@@ -159,6 +237,44 @@ class D3Term:
         self.last = self.engine.compute_many(z, pos.cpu().numpy(), self.cells[ids], self.pbcs[ids], n_atoms=self.n_atoms[ids])
         return (torch.as_tensor(np.concatenate([r['forces'] for r in self.last])).to(pos.device),
                 torch.as_tensor(np.array([r['energy'] for r in self.last])).to(pos.device))
+
+
+class D3DeviceTerm:
+    """`D3Term` with the state on the device: the `extra` of a batched driver that reads the driver's positions (and, under a
+    moving cell, its cells) where they are and returns (forces [N,3], energies [b], virial [b,6]) as device tensors -- one
+    `D3Engine.compute_device` per call, no copy in either direction.  Built from the arguments of `D3Term`.  The engine is
+    planned (`D3Engine.plan`) on the first call and again whenever `ids` changes (a repack of the batch); the returned tensors
+    are the plan's, overwritten by the next call.  `provides_virial` marks the third element for batch.BatchForces, which then
+    passes `cells_dev`; `status`: int32 [b] on the device, 1 for a system the last call could not evaluate (its forces,
+    energy and virial are NaN, see `D3Plan`)."""
+
+    provides_virial = True
+
+    def __init__(self, d3_engine: D3Engine, numbers, n_atoms, cells, pbcs):
+        self.engine = d3_engine
+        self.numbers, self.n_atoms = _as_host(numbers, np.int64).reshape(-1), _as_host(n_atoms, np.int64).reshape(-1)
+        B = len(self.n_atoms)
+        self.a_ptr = np.concatenate([[0], np.cumsum(self.n_atoms)])
+        self.cells = _as_host(cells, np.float64).reshape(B, 3, 3)
+        self.pbcs = np.broadcast_to(_as_host(pbcs, bool).reshape(-1, 3), (B, 3))
+        self._ids = self._plan = None
+        self.n_plans = 0
+
+    @property
+    def status(self):
+        return None if self._plan is None else self._plan.status
+
+    def __call__(self, pos, seg_ptr, ids, cells_dev=None):
+        ids = np.asarray(ids, np.int64)
+        moving = cells_dev is not None
+        if (self._plan is None or self._plan is not getattr(self.engine, '_plan', None) or self._plan.cells_move != moving
+                or not np.array_equal(ids, self._ids)):
+            z = np.concatenate([self.numbers[self.a_ptr[b]:self.a_ptr[b + 1]] for b in ids])
+            self._plan = self.engine.plan(z, self.n_atoms[ids], self.cells[ids], self.pbcs[ids], cells_move=moving, device=pos.device)
+            self._ids = ids.copy()
+            self.n_plans += 1
+        p = self.engine.compute_device(self._plan, pos, cells_dev)
+        return p.forces, p.energy, p.virial
 
 
 class D3Calculator(ManyAtomsMixin, Calculator):
@@ -253,41 +369,65 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         a, b = (c.compute_many(numbers_list, positions_list, cells, pbcs) for c in self.calcs)
         return [self._sum(x, y) for x, y in zip(a, b)]
 
-    def _d3_term(self, numbers_list, positions_list, cells, pbcs) -> D3Term:
-        """the D3 side of a batched driver, validated on the host (Z range, cells after the box rule)"""
+    def _d3_term(self, numbers_list, positions_list, cells, pbcs, d3_term: str = 'host'):
+        """the D3 side of a batched driver, validated on the host (Z range, cells after the box rule): a `D3Term`, or with
+        d3_term = 'device' a `D3DeviceTerm`"""
         d3 = self.calcs[1]
         if len(numbers_list) != len(positions_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
         bt = prepare_d3_batch(numbers_list, positions_list, cells, pbcs, d3.rthr, d3.cnthr)
-        return D3Term(d3.engine, bt.numbers, np.diff(bt.atom_ptr), cells, pbcs)
+        return (D3DeviceTerm if d3_term == 'device' else D3Term)(d3.engine, bt.numbers, np.diff(bt.atom_ptr), cells, pbcs)
 
-    def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+    @staticmethod
+    def _check_d3_term(d3_term) -> None:
+        if d3_term not in ('host', 'device'):
+            raise ValueError(f"d3_term = {d3_term!r}: 'host' (the D3 batch is prepared on the host each step) or 'device' (the D3 "
+                             'term stays on the device) is required')
+
+    def relax_many(self, numbers_list, positions_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, d3_term: str = 'host',
+                   **kw) -> List[Dict[str, Any]]:
         """`SevenNetCalculator.relax_many` on the sum of the model's and the D3 forces (sevennet_amd.relax): one dict per
-        system with the keys of `compute` plus `positions`, `converged` and `n_steps`; the results are `compute_many` at the
-        returned positions, the counters are kept as `self.relax_info`.  `D3Engine.compute_many` prepares its batch on the
-        host, so this path copies the positions down and the D3 forces up once per step (the model's forces and the
-        optimizer state stay on the device).  Fixed cells only: relax_cell=True raises ValueError, because the D3 term reaches
-        the optimizer through the `extra` contract, which carries no virial."""
-        if kw.get('relax_cell'):
-            raise ValueError('relax_cell is not available with D3: the D3 term reaches the optimizer through the `extra` contract, '
-                             'which carries forces and energies but no virial, so its cell force is unknown')
+        system with the keys of `compute` plus `positions`, `converged` and `n_steps` (with relax_cell: `cell` and `status`); the
+        results are `compute_many` at the returned positions (and cells), the counters are kept as `self.relax_info`.
+        d3_term = 'host' (the default): `D3Engine.compute_many` prepares its batch on the host, so this path copies the
+        positions down and the D3 forces up once per step (the model's forces and the optimizer state stay on the device).
+        Fixed cells only: relax_cell=True raises ValueError, because the host term reaches the optimizer through the `extra`
+        contract, which carries no virial.
+        d3_term = 'device': the D3 term is a `D3DeviceTerm` -- planned once (and at each repack), evaluated from the driver's
+        device positions, nothing copied per step.  It hands the optimizer a virial too, so relax_cell=True relaxes the cells
+        under model + D3 (systems periodic along all three axes, at most batch.BATCH_MAX_ATOMS atoms, as for the model alone).
+        The plan leaves each system's lattice sums room for one more repetition per axis than its starting cell needs; a cell
+        that shrinks beyond that makes the D3 virial NaN, which the step kernel refuses: the system comes back as it was
+        before that step with status 'cell_failed'."""
+        self._check_d3_term(d3_term)
+        if kw.get('relax_cell') and d3_term == 'host':
+            raise ValueError("relax_cell is not available with d3_term='host': that D3 term reaches the optimizer through the `extra` "
+                             "contract, which carries forces and energies but no virial, so its cell force is unknown (pass "
+                             "d3_term='device', whose term carries one)")
         snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), list(positions_list)
-        term = self._d3_term(numbers_list, positions_list, cells, pbcs)
+        term = self._d3_term(numbers_list, positions_list, cells, pbcs, d3_term)
         results = snet.relax_many(numbers_list, positions_list, cells, pbcs, fmax=fmax, steps=steps, extra=term, **kw)
         self.relax_info = snet.relax_info
-        at_final = d3.compute_many(numbers_list, [r['positions'] for r in results], cells, pbcs)
+        final_cells = np.stack([r['cell'] for r in results]) if kw.get('relax_cell') else cells
+        at_final = d3.compute_many(numbers_list, [r['positions'] for r in results], final_cells, pbcs)
         return [self._sum(a, b) for a, b in zip(results, at_final)]
 
-    def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
+    def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, d3_term: str = 'host',
+                **kw) -> List[Dict[str, Any]]:
         """`SevenNetCalculator.md_many` on the sum of the model's and the D3 forces (sevennet_amd.md): one dict per system
         with the summed keys of `compute` at the returned positions plus `positions`, `velocities`, `e_pot` (D3 energy
-        included), `e_kin`, `temperature` (and `trajectory`); the counters are kept as `self.md_info`.  As in `relax_many`,
-        the D3 batch is prepared on the host: this path copies the positions down and the D3 forces up once per step."""
-        snet = self.calcs[0]
+        included), `e_kin`, `temperature` (and `trajectory`); the counters are kept as `self.md_info`.  d3_term as in
+        `relax_many`: with 'host' the D3 batch is prepared on the host (this path copies the positions down and the D3 forces
+        up once per step), with 'device' the D3 term stays on the device and the D3 share of the results is one
+        `compute_many` at the returned positions."""
+        self._check_d3_term(d3_term)
+        snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), list(positions_list)
-        term = self._d3_term(numbers_list, positions_list, cells, pbcs)
+        term = self._d3_term(numbers_list, positions_list, cells, pbcs, d3_term)
         results = snet.md_many(numbers_list, positions_list, masses_list, cells, pbcs, dt, steps, extra=term, **kw)
         self.md_info = snet.md_info
+        if d3_term == 'device':
+            return [self._sum(a, b) for a, b in zip(results, d3.compute_many(numbers_list, [r['positions'] for r in results], cells, pbcs))]
         # the model's results and the D3 results of the last step's evaluations, both at the returned positions
         return [self._sum(a, D3Calculator._results(b)) for a, b in zip(results, term.last)]

@@ -215,7 +215,8 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     system's noise is counted under, default 0..B-1 -- a system run alone under the id it had in a batch sees the same noise.
     extra: optional callable with the contract of `batch.BatchForces` (positions fp64 [N,3] on the device, seg_ptr int64 [B+1]
     on the host, ids int64 [B]: the index of each system in this call) -> forces [N,3], or (forces, energy_per_system [B]),
-    added to the model's each step (the energies go into the potential-energy log).
+    added to the model's each step (the energies go into the potential-energy log).  An extra that also returns a virial
+    (`provides_virial = True`, d3.D3DeviceTerm) is taken as well; at fixed cells its virial is not used.
 
     Schedule: F0 = f(x0), one launch that starts step 1; then per step Fk = f(xk) and one launch that finishes step k and
     starts step k + 1 (the last one only finishes).  steps = 0: one force call, one launch that moves nothing.

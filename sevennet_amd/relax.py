@@ -229,7 +229,8 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
                    min_height: float):
     """The variable-cell relaxation loop.  forces: a BatchForces, or any object with its call interface (pos, ids, cells_dev=) ->
     (graph with seg_ptr, output with `forces` fp32 [N,3] and `virial_per_system` fp64 [b,6], extra forces or None, ...), its
-    counters (n_force_calls, system_steps_evaluated), `n_atoms` and `engine.dev`.  cells [B,3,3]: the caller's, which stay the
+    counters (n_force_calls, system_steps_evaluated), `n_atoms` and `engine.dev`, and optionally `virial_extra` (fp64 [b,6] on the
+    device or None: the virial that goes with the extra forces, added to the model's in the step kernel).  cells [B,3,3]: the caller's, which stay the
     reference cells.  Per step: one graph build from the device cells, one engine call, one `snet_fire_cell_step`, one readback
     (n_active).  -> (positions fp64 [N,3] and cells fp64 [B,9] on the device in the caller's order, n_steps [B], status [B] (0
     step cap, 1 converged, 2 the kernel's guard refused the next cell), info)"""
@@ -254,7 +255,8 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
         for _ in range(int(steps)):
             g, out, fx = forces(pos, book.ids, cells_dev=cell)[:3]
             fire_cell_step(pos, vel, cell, vel_cell, cell0, out['forces'], out['virial_per_system'], g.seg_ptr, dt, alpha, n_pos,
-                           active, n_steps, status, fmax_sys, n_active, fmax, params, cell_params, min_height, fx)
+                           active, n_steps, status, fmax_sys, n_active, fmax, params, cell_params, min_height, fx,
+                           getattr(forces, 'virial_extra', None))
             fire_launches += 1
             left = int(n_active.item())   # the one readback of the step
             if left == 0:
@@ -301,20 +303,23 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
     six 0/1 Voigt flags (xx,yy,zz,yz,xz,xy) of the strain components that may change (default: all); hydrostatic_strain: the
     cell changes by a uniform scaling only; constant_volume: the trace of the cell force is projected out.  Every system must
     be periodic along all three axes and one of the batched neighbor kernel (at most batch.BATCH_MAX_ATOMS atoms, no height
-    below cutoff / 64); `extra` is refused, because its contract carries forces and energies but no virial.  The results gain
+    below cutoff / 64); a plain `extra` is refused, because its contract carries forces and energies but no virial -- one marked
+    `provides_virial = True` (d3.D3DeviceTerm; batch.BatchForces) is taken, and its virial enters the cell force.  A NaN in
+    that virial fails the step kernel's guard like any other non-finite step ('cell_failed' below).  The results gain
     `cell` [3,3] fp64 (energy, forces and stress are those at the returned positions AND cell) and `status`: 'converged',
     'steps' (the step cap) or 'cell_failed' (the step kernel refused a next cell that was not finite, inverted, or flatter than
     cutoff / 64: the system is returned as it was before that step); `converged` is True for the first only."""
     params = check_fire_params(fmax, steps, repack_below, fire)
     cell_params = check_cell_params(scalar_pressure, cell_mask, hydrostatic_strain, constant_volume)
-    if relax_cell and extra is not None:
+    if relax_cell and extra is not None and not getattr(extra, 'provides_virial', False):
         raise ValueError('relax_cell with extra: the contract of `extra` carries forces and energies but no virial, so the cell '
-                         'force of the extra term is unknown (for D3 under a moving cell, relax at fixed cells instead)')
+                         'force of the extra term is unknown (an extra marked `provides_virial = True` returns one; for D3 that is '
+                         "d3.D3DeviceTerm, SevenNetD3Calculator.relax_many(d3_term='device'))")
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
     if relax_cell:
         check_cell_relax_systems(n_at, cells, pbcs, cutoff)
-        forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff)
+        forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
         final, final_cells, n_steps, status, info = fire_cell_loop(
             forces, positions, cells, fmax=fmax, steps=steps, repack_below=repack_below, params=params, cell_params=cell_params,
             min_height=cutoff / _MAX_IMAGE_REACH)
