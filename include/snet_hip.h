@@ -31,8 +31,9 @@ extern "C" {
 /* Bumped whenever an exported signature or a file format changes incompatibly; every host checks snet_abi_version() against
  * the header it was built from (sevennet_amd/_lib.py, lammps/pair_*_hip.cpp).  History: 1 = rounds 1-3; 2 = round 4 (snet_nl_grid /
  * _bin / _count / _fill gained the open-axis arguments, .snet files moved to "SNETMDL4") and round 5 (pair_failed); 3 = round 6 (the
- * unwired two-fp16-term grouped GEMM snet_gemm_f16_size / _pack / snet_gemm_grouped_f16 left the library). */
-#define SNET_ABI_VERSION 3
+ * unwired two-fp16-term grouped GEMM snet_gemm_f16_size / _pack / snet_gemm_grouped_f16 left the library); 4 = snet_layer0_* (layer 0
+ * from per-atom radial moments). */
+#define SNET_ABI_VERSION 4
 
 /* ---- housekeeping ------------------------------------------------------- */
 int snet_abi_version(void);
@@ -261,6 +262,34 @@ int snet_conv_bwd_fused_tangent(const snet_fused_plan *plan, const float *x, con
                                 const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles, float scale, const float *g_out,
                                 float *g_xe, const float *edge_vec, float *g_vec, const float *x_rowmax, const float *g_rowmax,
                                 void *stream);
+/* ---- first interaction layer from per-atom radial moments --------------------------------------------------------------
+ * Layer 0's source rows depend on the species alone, x[src(e)] = table[species(src(e))] (node embedding -> SI1, the species-only
+ * tables of both hosts), its inputs are scalars and its paths (0, l -> l) with unit diagonal coupling.  Per edge the message is
+ * scale Y_e[q] table[s,u] sum_k h2_e[k] W2[k, l(q) mul + u], and the sum over a node's edges commutes with the W2 product.  With
+ *   B_l[(s,k), u] = W2[k, l mul + u] table[s, u] scale        (folded in fp64 at plan creation, rounded once)
+ * reverse:  Bm_i[q,s,k] = sum_u g_out_i[q,u] B_l(q)[(s,k),u]       (one grouped split-precision GEMM), then per edge, in fp32 FMAs,
+ *           dE/dY_e[q] = sum_k h2_e[k] Bm_i[q,slot(e),k] and dE/d|r_e| = sum_q Y_e[q] sum_k h2d_e[k] Bm_i[q,slot(e),k],
+ *           both ACCUMULATED into g_vec[E,3] as snet_conv_bwd_fused_tangent does (dsh, r_e / |r_e|); no atomics.
+ * The W2 product runs once per atom instead of once per edge, and nothing is an fp16 operand: no x_rowmax / g_rowmax.  (The forward
+ * pass keeps snet_conv_fwd_fused: its moments form missed the accuracy bar)
+ *   plan       conv = the layer's shape (refused unless dx = mul scalars, wn = (lmax + 1) mul, dout = nsh mul, 16 | mul <= 512,
+ *              lmax <= 3: the CALLER vouches for the paths being (0, l -> l) in l order); W2_host[64, wn] and scale as the fused
+ *              kernels take them; table_host[n_slots, mul], row s = the source row of the species in slot s; 1 <= n_slots <= 4
+ *   species_slot  int32[n_species] (device): slot of each species in [0, n_slots); species of an edge = types[src[e]]
+ *   h2 / h2d / w_row / row_ptr / src / sh / dsh / edge_vec: as snet_conv_bwd_fused_tangent; n_nodes destination rows
+ *   scratch    snet_layer0_scratch_size(plan, n_nodes) = n_nodes nsh n_slots 64 floats (Bm), owned by the caller                */
+typedef struct snet_layer0_plan snet_layer0_plan;
+int snet_layer0_plan_create(const snet_conv_plan *conv, const float *W2_host, const float *table_host, float scale,
+                            int32_t n_slots, snet_layer0_plan **plan);
+void snet_layer0_plan_destroy(snet_layer0_plan *plan);
+/* the fold itself, on the host (what the plan packs): bt_host[mul, 64 n_slots] = B_l^T, bt[u, s 64 + k] = W2[k, l mul + u] table[s, u] scale */
+int snet_layer0_fold(const float *W2_host, int32_t wn, int32_t mul, const float *table_host, float scale, int32_t n_slots, int32_t l,
+                     float *bt_host);
+int64_t snet_layer0_scratch_size(const snet_layer0_plan *plan, int64_t n_nodes);
+int snet_layer0_conv_bwd(const snet_layer0_plan *plan, const float *g_out, const float *h2, const float *h2d, const int32_t *w_row,
+                         const int32_t *row_ptr, const int32_t *src, const int32_t *types, const int32_t *species_slot,
+                         const float *sh, const float *dsh, const float *edge_vec, int64_t n_nodes, float *scratch, float *g_vec,
+                         void *stream);
 /* g_xe[E,dx] of snet_conv_bwd_fused is an intermediate with its own row layout: the 16-channel chunks of a row are stored in
  * the order the kernel produces them ([x block][channel tile][component]: each (block, tile) writes one contiguous run per
  * edge instead of half cache lines).  chunk_pos[s] (dx / 16 entries, host) = position of standard chunk s in the row;
@@ -559,6 +588,10 @@ typedef int (*snet_halo_fn)(void *user, float *x, int64_t n_total, int64_t n_loc
  * its construction reads a count back, i.e. synchronises the stream --, the edges grouped by source, per-species row lists)
  * across evaluations for as long as the caller passes the SAME device index arrays (row_ptr, src, eperm, w_row; same counts)
  * and has not called snet_model_topology_changed.  A caller that rewrites those arrays in place must call it.  Off by default.
+ * Models of more than 4 species also keep the set of species that occur among the n_total atoms (layer 0's species slots,
+ * snet_layer0_*) under the same rule, keyed by the `types` device array: a caller that rewrites `types` in place must call
+ * snet_model_topology_changed as well.  With the cache off such a model reads `types` back on every evaluation (one n_total-sized
+ * copy and one stream synchronisation per step); models of at most 4 species never do.
  * snet_model_eval_syncs: stream synchronisations issued inside snet_model_eval since the model was loaded (diagnostic). */
 /* Bricks of a spatial decomposition that number their local atoms INTERIOR FIRST (rows [0, n_interior) have no ghost source;
  * sevennet_amd.parallel.BrickGraph.n_interior) let the sequencer run the interior rows of the fused convolutions while the
@@ -566,6 +599,10 @@ typedef int (*snet_halo_fn)(void *user, float *x, int64_t n_total, int64_t n_loc
  * model).  0 (default) = no split.  Applies to the following evaluations until set again.                              */
 int snet_model_set_interior(snet_model *model, int64_t n_interior);
 int snet_model_set_topology_cache(snet_model *model, int32_t enable);
+/* layer 0's reverse pass through snet_layer0_conv_bwd (enable != 0; the default unless SNET_LAYER0_MOMENTS=0 is in the environment at
+ * load time) or through the fused kernel (0), where the model is eligible at all: its file carries the metadata key layer0_moments=1
+ * and the shape passes snet_layer0_plan_create.  Applies to the following evaluations.  For A/B runs and tests. */
+int snet_model_set_layer0_moments(snet_model *model, int32_t enable);
 int snet_model_topology_changed(snet_model *model);
 int64_t snet_model_eval_syncs(const snet_model *model);
 int snet_model_set_halo(snet_model *model, snet_halo_fn forward, snet_halo_fn reverse, void *user,

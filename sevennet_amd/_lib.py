@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 3   # == SNET_ABI_VERSION of include/snet_hip.h (tests/test_abi_cpu.py keeps the two in step)
+ABI_VERSION = 4   # == SNET_ABI_VERSION of include/snet_hip.h (tests/test_abi_cpu.py keeps the two in step)
 LIB_PATH = os.environ.get('SNET_HIP_LIB') or os.path.join(_HERE, 'libsnet_hip.so')  # env: kernel experiments
 
 c_f32p = C.c_void_p   # device float*
@@ -93,6 +93,13 @@ SIGNATURES = {
     'snet_conv_bwd_fused_tangent': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p,
                                               c_i32p, C.c_int64, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                               c_stream]),
+    'snet_model_set_layer0_moments': (C.c_int, [C.c_void_p, C.c_int32]),
+    'snet_layer0_plan_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
+    'snet_layer0_fold': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
+    'snet_layer0_plan_destroy': (None, [C.c_void_p]),
+    'snet_layer0_scratch_size': (C.c_int64, [C.c_void_p, C.c_int64]),
+    'snet_layer0_conv_bwd': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
+                                       C.c_int64, c_f32p, c_f32p, c_stream]),
     'snet_fused_plan_gxe_chunks': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     'snet_segment_sum_rows_chunked': (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int64, C.c_int32, c_i32p, c_f32p, c_stream]),
     'snet_edge_vectors': (C.c_int, [c_f64p, c_i32p, c_i32p, c_f64p, C.c_int64, c_f32p, c_stream]),

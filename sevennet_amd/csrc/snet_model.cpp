@@ -281,6 +281,21 @@ struct snet_model {
     const int v = e ? atoi(e) : SNET_FUSED_TERMS_DEFAULT;
     return v >= 1 && v <= 4 ? v : SNET_FUSED_TERMS_DEFAULT;
   }();
+  // Layer 0's reverse pass from per-atom products (snet_layer0_conv_bwd, engine.py's `layer0_moments`); snet_model_set_layer0_moments(0)
+  // or SNET_LAYER0_MOMENTS=0 (the default of a host that never calls the setter) keep the fused kernel: A/B runs and tests.  Plans are
+  // folded per set of species slots: every species of a model of at most 4, else the species that occur among the graph's n_total
+  // atoms (read back when the topology cache misses), at most 4 -- engine.py's rule, so that both hosts run the same launches.
+  bool l0_mode = [] {
+    const char *e = getenv("SNET_LAYER0_MOMENTS");
+    return e == nullptr || strcmp(e, "0") != 0;
+  }();
+  bool l0_shape_ok = false;           // layer 0's shape and radial network are inside snet_layer0_plan_create's domain
+  std::vector<float> h0_host;         // host copy of h0_table
+  struct L0Plan { snet_layer0_plan *plan; int32_t *slot; int n_slots; };
+  std::map<std::vector<int32_t>, L0Plan> l0_plans;
+  std::vector<int32_t> l0_present;    // species set of the cached topology (models of more than 4 species)
+  const void *l0_key_types = nullptr;
+  int64_t l0_key_nt = -1;
 };
 
 constexpr int64_t OVERLAP_MAX_EDGES = 1000000;  // same policy as engine.py
@@ -415,6 +430,7 @@ extern "C" int snet_model_load_memory(const void *blob, int64_t n_bytes, snet_mo
     if (good) {
       std::vector<float> h0 = r.farr((size_t)m->n_species * dx0), sc0 = r.farr((size_t)m->n_species * gin0);
       good = r.ok && dev_upload(h0, &m->h0_table) && dev_upload(sc0, &m->sc0_table);
+      m->h0_host = h0;
     }
   }
   if (good && ro_kind == 1) {
@@ -455,6 +471,28 @@ extern "C" int snet_model_load_memory(const void *blob, int64_t n_bytes, snet_mo
     const int nm = r.i32();
     good = r.ok && nm >= 0 && nm <= (1 << 20) && (int64_t)(r.end - r.p) == nm;
     if (good) m->meta.assign(reinterpret_cast<const char *>(r.p), (size_t)nm);
+  }
+  // Layer 0's reverse pass from per-atom products: the paths, offsets and coupling terms were checked where the file was written
+  // (metadata key layer0_moments=1, model_spec.layer0_moments_eligible -- the predicate of the Python host, so both hosts decide
+  // alike; a file without the key keeps the fused kernel); dimensions and the radial network are checked here.
+  if (good && ("\n" + m->meta).find("\nlayer0_moments=1\n") != std::string::npos) {
+    const Layer &L0 = m->layers[0];
+    snet_layer0_plan *probe = nullptr;
+    const int nsl = m->n_species <= 4 ? m->n_species : 1;
+    if (L0.fused && L0.mlp[1] == 64 && L0.mlp[2] == 64 &&
+        snet_layer0_plan_create(L0.conv, snet::mlp_plan_w2_host(L0.mlp_plan), m->h0_host.data(), L0.conv_scale, nsl, &probe) == 0) {
+      m->l0_shape_ok = true;
+      if (m->n_species <= 4) {   // every species its own slot: the one plan this model needs
+        std::vector<int32_t> all(m->n_species);
+        for (int s = 0; s < m->n_species; ++s) all[s] = s;
+        int32_t *ds = nullptr;
+        good = hipMalloc((void **)&ds, all.size() * 4) == hipSuccess &&
+               hipMemcpy(ds, all.data(), all.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        m->l0_plans[all] = {probe, ds, m->n_species};
+      } else {
+        snet_layer0_plan_destroy(probe);
+      }
+    }
   }
   } catch (const std::exception &e) {  // nothing may propagate through an extern "C" entry point
     snet::set_error(std::string("exception: ") + e.what());
@@ -500,6 +538,10 @@ extern "C" void snet_model_destroy(snet_model *m) {
   for (float *w : m->fcn_w) if (w) (void)hipFree(w);
   for (float *w : m->fcn_wt) if (w) (void)hipFree(w);
   if (m->one_d) (void)hipFree(m->one_d);
+  for (auto &kv : m->l0_plans) {
+    snet_layer0_plan_destroy(kv.second.plan);
+    if (kv.second.slot) (void)hipFree(kv.second.slot);
+  }
   for (auto &L : m->layers) {
     snet_fused_plan_destroy(L.fused);
     snet_fused_plan_destroy(L.tfused);
@@ -573,19 +615,80 @@ extern "C" int snet_model_set_interior(snet_model *m, int64_t n_interior) {
   return 0;
 }
 
+extern "C" int snet_model_set_layer0_moments(snet_model *m, int32_t enable) {
+  SNET_REQUIRE(m != nullptr, "snet_model_set_layer0_moments: null model");
+  m->l0_mode = enable != 0;
+  return 0;
+}
+
 extern "C" int snet_model_set_topology_cache(snet_model *m, int32_t enable) {
   SNET_REQUIRE(m != nullptr, "snet_model_set_topology_cache: null model");
   m->topo_cache = enable != 0;
   m->topo_valid = false;
+  m->l0_key_nt = -1;
   return 0;
 }
 
 extern "C" int snet_model_topology_changed(snet_model *m) {
   SNET_REQUIRE(m != nullptr, "snet_model_topology_changed: null model");
   m->topo_valid = false;
+  m->l0_key_nt = -1;
   m->types_prev.clear();
   return 0;
 }
+
+namespace {
+// the snet_layer0_* plan of this evaluation's species set (*out stays null: the fused kernels run)
+int layer0_select(snet_model *m, const int32_t *types, int64_t NT, hipStream_t st, const snet_model::L0Plan **out) {
+  *out = nullptr;
+  std::vector<int32_t> present;
+  if (m->n_species <= 4) {
+    for (int s = 0; s < m->n_species; ++s) present.push_back(s);
+  } else {
+    if (!(m->topo_cache && m->l0_key_types == types && m->l0_key_nt == NT)) {
+      std::vector<int32_t> th((size_t)NT);
+      SNET_REQUIRE(hipMemcpyAsync(th.data(), types, (size_t)NT * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                       hipStreamSynchronize(st) == hipSuccess, "snet_model_eval: read-back of the species failed");
+      ++m->eval_syncs;
+      std::vector<char> seen((size_t)m->n_species, 0);
+      for (int32_t v : th) {
+        SNET_REQUIRE(v >= 0 && v < m->n_species, "snet_model_eval: species index out of range");
+        seen[v] = 1;
+      }
+      m->l0_present.clear();
+      for (int s = 0; s < m->n_species; ++s)
+        if (seen[s]) m->l0_present.push_back(s);
+      m->l0_key_types = types;
+      m->l0_key_nt = NT;
+    }
+    present = m->l0_present;
+    if (present.empty() || present.size() > 4) return 0;
+  }
+  auto it = m->l0_plans.find(present);
+  if (it == m->l0_plans.end()) {
+    const Layer &L0 = m->layers[0];
+    std::vector<float> table(present.size() * (size_t)L0.dx);
+    std::vector<int32_t> slot((size_t)m->n_species, 0);
+    for (size_t i = 0; i < present.size(); ++i) {
+      slot[present[i]] = (int32_t)i;
+      memcpy(&table[i * L0.dx], &m->h0_host[(size_t)present[i] * L0.dx], (size_t)L0.dx * 4);
+    }
+    snet_model::L0Plan e{nullptr, nullptr, (int)present.size()};
+    if (int rc = snet_layer0_plan_create(L0.conv, snet::mlp_plan_w2_host(L0.mlp_plan), table.data(), L0.conv_scale, e.n_slots, &e.plan))
+      return rc;
+    if (hipMalloc((void **)&e.slot, slot.size() * 4) != hipSuccess ||
+        hipMemcpy(e.slot, slot.data(), slot.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      snet_layer0_plan_destroy(e.plan);
+      if (e.slot) (void)hipFree(e.slot);
+      snet::set_error("snet_model_eval: upload of the species slots failed");
+      return 1;
+    }
+    it = m->l0_plans.emplace(present, e).first;
+  }
+  *out = &it->second;
+  return 0;
+}
+}  // namespace
 
 extern "C" int64_t snet_model_eval_syncs(const snet_model *m) { return m ? m->eval_syncs : -1; }
 
@@ -664,6 +767,12 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     }
   }
 
+  // ---- layer 0's reverse pass from per-atom products (where its shape and this graph's species allow it)
+  const snet_model::L0Plan *l0 = nullptr;
+  if (m->l0_mode && m->l0_shape_ok && E > 0)
+    if (int rc0 = layer0_select(m, types, NT, st, &l0)) return rc0;
+  const size_t l0_scratch = l0 ? (size_t)snet_layer0_scratch_size(l0->plan, N) + 64 : 0;   // Bm [N, nsh, slots, 64]
+
   // ---- arena sizing
   size_t need = 0;
   auto add = [&](size_t n) { need += ((n * 4 + 255) / 256) * 256; };
@@ -676,7 +785,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     add((size_t)NT * L.dx); add(L.fused ? (size_t)WR * 64 : (size_t)WR * L.wn); add((size_t)N * L.gin);  // saved h, w | h2, y
     add((size_t)NT + 64);  // x_max (kept through the reverse pass)
     const size_t t = ((size_t)N * L.gin + 64) * 2 + (size_t)N * L.dmid * 2 + (size_t)E * (L.fused ? 64 : L.wn) + (size_t)E * L.dx +
-                     (size_t)NT * L.dx * 2 + (size_t)N * L.dout + (size_t)NT + (size_t)N + 4096;  // + x_max, g_max
+                     (size_t)NT * L.dx * 2 + (size_t)N * L.dout + (size_t)NT + (size_t)N + 4096 + l0_scratch;  // + x_max, g_max
     trans = trans > t ? trans : t;
   }
   size_t wn_max = 0;
@@ -720,7 +829,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   for (int t = 0; t < Lc; ++t) {
     saved[t].h = A.f((size_t)NT * m->layers[t].dx);
     saved[t].w = A.f(m->layers[t].fused ? (size_t)WR * 64 : (size_t)WR * m->layers[t].wn);
-    const bool tg = m->layers[t].fused != nullptr && snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0;
+    const bool tg = m->layers[t].fused != nullptr && (snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0 || (t == 0 && l0 != nullptr));
     saved[t].wd = tg ? A.f((size_t)WR * 64) : nullptr;
     all_tangent = all_tangent && tg;
     saved[t].y = A.f((size_t)N * m->layers[t].gin);
@@ -998,7 +1107,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     int32_t dims[8];
     int nj = 0;
     for (int t = 0; t <= Lc; ++t) {
-      if (t < Lc && m->layers[t].fused) {
+      if (t < Lc && m->layers[t].fused && !(t == 0 && l0 != nullptr)) {   // (snet_layer0_conv_bwd has no fp16 operand)
         x_max_of[t] = A.f((size_t)NT + 64);
         xs[nj] = saved[t].h; outs[nj] = x_max_of[t]; rows[nj] = NT; dims[nj] = m->layers[t].dx; ++nj;
       }
@@ -1014,7 +1123,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     A.off = mark2;
     float *g_y = A.f((size_t)N * L.gin);
     // fp16 operands of the fused reverse kernel: bound of every row of g_m = SI2^T g_y (Cauchy-Schwarz), taken in the same pass
-    float *g_max = (L.fused && E > 0 && m->fused_terms == 4) ? A.f((size_t)N) : nullptr;
+    float *g_max = (L.fused && E > 0 && m->fused_terms == 4 && !(t == 0 && l0 != nullptr)) ? A.f((size_t)N) : nullptr;
     if ((rc = snet_gate_bwd_norm(saved[t].y, g_x, g_y, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(),
                                  g_max ? L.si2.t_norm : 0.f, g_max, st)))
       return rc;
@@ -1038,7 +1147,12 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       };
       const bool rsplit = hsplit && t > 0;
       const bool packed = L.tile_mode != 0;
-      auto bwd_all = [&]() -> int { return packed ? bwd_tiles(ptile_e0, ptile_nodes, pn_tiles) : bwd_tiles(tile_ptr, tile_node, n_tiles); };
+      auto bwd_all = [&]() -> int {
+        if (t == 0 && l0 != nullptr)   // transposed grouped GEMM per atom, then one pass over the edges: g_vec += spherical and radial part
+          return snet_layer0_conv_bwd(l0->plan, g_m, saved[t].w, saved[t].wd, pairs ? w_row : nullptr, row_ptr, src, types, l0->slot, sh,
+                                      dsh, edge_vec, N, A.f(l0_scratch), g_vec, st);
+        return packed ? bwd_tiles(ptile_e0, ptile_nodes, pn_tiles) : bwd_tiles(tile_ptr, tile_node, n_tiles);
+      };
       if (!rsplit && (rc = bwd_all())) return rc;
       if (t > 0) {
         float *g_h = A.f((size_t)NT * L.dx);

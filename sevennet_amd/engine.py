@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model_spec import (ACT_CST, ACT_ID, LinearSpec, ModelSpec, build_model_spec, folded_readout, linear_modal_bias,
-                         linear_weight_matrices, species_only_tables, transposed_scalar_conv)
+from .model_spec import (ACT_CST, ACT_ID, LinearSpec, ModelSpec, build_model_spec, folded_readout, layer0_moments_eligible,
+                         linear_modal_bias, linear_weight_matrices, species_only_tables, transposed_scalar_conv)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -300,7 +300,7 @@ class HipForceEngine:
     def __init__(self, config: dict, state_dict: Dict[str, np.ndarray], device='cuda:0', mlp_mode: str = 'bf16x6',
                  linear_mode: str = 'bf16x6', fused='auto', fused_terms='f16x3', modal=None, overlap: bool = True,
                  mlp_tail: bool = True, transposed_conv: bool = True, species_tables: bool = True,
-                 fold_readout: bool = True, tangent: bool = True):
+                 fold_readout: bool = True, tangent: bool = True, layer0_moments: bool = True):
         """mlp_mode / linear_mode: 'bf16x6' (split-precision MFMA, fp32-class accuracy, default) or
         'fp32' (exact fp32 MFMA) for the fused radial MLP / the node-level equivariant linears.
         fused: 'auto' (default) / True / False / 'fwd' / 'bwd' -- run the radial MLP's last layer INSIDE the
@@ -334,18 +334,11 @@ class HipForceEngine:
         the reverse-mode path (g_h2 / in-kernel tail -> g_emb -> snet_edge_embed_bwd), kept for A/B runs and as the tests' reference.
         modal: fidelity channel (name from config['_modal_map'] or index) of a multi-modal model; the
         one-hot inputs of its linears become constant biases, shift/scale rows are selected at load.
+        layer0_moments: layer 0's reverse pass from one W2 product per atom (snet_layer0_conv_bwd); see _init_layer0.
         """
-        if mlp_mode not in ('bf16x6', 'fp32') or linear_mode not in ('bf16x6', 'fp32'):
-            raise ValueError("mlp_mode / linear_mode must be 'bf16x6' or 'fp32'")
-        if fused not in ('auto', True, False, 'fwd', 'bwd'):
-            raise ValueError("fused must be 'auto', True, False, 'fwd' or 'bwd'")
+        self.fused_terms, self.fused_mode = self._check_modes(mlp_mode, linear_mode, fused, fused_terms)
         self.mlp_mode = mlp_mode
         self.linear_mode = linear_mode
-        codes = {'bf16': 1, 'bf16x3': 2, 'bf16x6': 3, 'f16x3': 4}
-        if fused_terms not in codes and fused_terms not in codes.values():
-            raise ValueError(f"fused_terms must be one of {sorted(codes)} (or the C-ABI code 1..4)")
-        self.fused_terms = int(codes.get(fused_terms, fused_terms))
-        self.fused_mode = {v: k for k, v in codes.items()}[self.fused_terms]
         self.overlap, self.halo_split = bool(overlap), True   # False: exchange, then the whole convolution (A/B measurements of the overlap)
         self._side = None  # second stream, created on first use
         self._acc_descs = {}  # id(descriptor array) -> its all-accumulating copy (the arrays live as long as the engine)
@@ -408,7 +401,7 @@ class HipForceEngine:
                                                                     ACT_ID[sp.act_radial], ACT_CST[sp.act_radial],
                                                                     1 if mlp_mode == 'bf16x6' else 0, C.byref(mp)),
                                'snet_radial_mlp_plan_create')
-                    L.mlp_plan = mp
+                    L.mlp_plan, L.w2_host = mp, hw[2]
                 L.scale = 1.0 / float(sd[f'{ls.t}_convolution.denominator'][0])
                 if ls.conv.tag not in _lib.compiled_conv_tags():   # a model outside sevennet_amd/shapes.py: compile its shape now
                     from .jit import ensure_conv_shape
@@ -497,9 +490,25 @@ class HipForceEngine:
         self.act_radial = ACT_ID[sp.act_radial]
         self.act_cst = ACT_CST[sp.act_radial]
         self.needs_species_rows = any(ls.sc is not None and ls.sc.n_species for ls in sp.layers)
+        self._init_layer0(layer0_moments)
+
+    @staticmethod
+    def _check_modes(mlp_mode, linear_mode, fused, fused_terms):
+        """argument checks of the constructor -> (C-ABI code, name) of the fused kernels' precision mode"""
+        if mlp_mode not in ('bf16x6', 'fp32') or linear_mode not in ('bf16x6', 'fp32'):
+            raise ValueError("mlp_mode / linear_mode must be 'bf16x6' or 'fp32'")
+        if fused not in ('auto', True, False, 'fwd', 'bwd'):
+            raise ValueError("fused must be 'auto', True, False, 'fwd' or 'bwd'")
+        codes = {'bf16': 1, 'bf16x3': 2, 'bf16x6': 3, 'f16x3': 4}
+        if fused_terms not in codes and fused_terms not in codes.values():
+            raise ValueError(f"fused_terms must be one of {sorted(codes)} (or the C-ABI code 1..4)")
+        code = int(codes.get(fused_terms, fused_terms))
+        return code, {v: k for k, v in codes.items()}[code]
 
     def __del__(self):
         try:
+            for pl, _, _ in (getattr(self, 'l0_plans', None) or {}).values():
+                self.lib.snet_layer0_plan_destroy(pl)
             for L in getattr(self, 'layers', []):
                 if getattr(L, 'fplan', None) is not None:
                     self.lib.snet_fused_plan_destroy(L.fplan)
@@ -612,6 +621,50 @@ class HipForceEngine:
                                                  self.act_cst, _stream()), 'snet_act_bwd')
                 g = ga
 
+    # ------------------------------------------------- layer 0 from moments
+    def _init_layer0(self, layer0_moments):
+        """layer0_moments: the reverse pass of the first interaction layer (species-only source rows, paths (0, l -> l)) from one
+        grouped GEMM per atom and a pass over the edges instead of the fused per-edge kernel (snet_layer0_conv_bwd); the
+        forward pass is untouched, so energies keep their bits.  False: the fused kernel, kept for A/B runs and as the tests'
+        reference.  Decided per shape here (model_spec.layer0_moments_eligible, species tables on, fused kernels in both
+        directions: they supply h2), per graph in _layer0_plan (at most 4 species)."""
+        L0 = self.layers[0]
+        self.l0_plans = None
+        if (layer0_moments and self.h0_table is not None and L0.fused_fwd and L0.fused_bwd
+                and layer0_moments_eligible(L0.spec.conv, L0.spec.mlp_dims)):
+            self.l0_plans, self.h0_host = {}, self.h0_table.cpu().numpy()
+
+    def _layer0_plan(self, g: Graph):
+        """(plan, species_slot, n_slots) of snet_layer0_* for this graph's species, or None (ineligible shape, switch off, no edges,
+        more than 4 species).  Models of at most 4 species give each its own slot; larger ones the species that occur in the graph
+        (rows of all n_total atoms, read back once per Graph), in ascending order -- the rule of the native sequencer."""
+        if self.l0_plans is None or g.n_edges == 0:
+            return None
+        ns = self.h0_host.shape[0]
+        present = tuple(range(ns)) if ns <= 4 else getattr(g, '_species_present', None)
+        if present is None:
+            present = g._species_present = tuple(int(v) for v in torch.unique(g.types).cpu())
+        if not 1 <= len(present) <= 4 or present[0] < 0 or present[-1] >= ns:
+            return None
+        if present not in self.l0_plans:
+            L0, plan = self.layers[0], C.c_void_p()
+            table = np.ascontiguousarray(self.h0_host[list(present)], np.float32)
+            _lib.check(self.lib.snet_layer0_plan_create(L0.plan, C.c_void_p(L0.w2_host.ctypes.data), C.c_void_p(table.ctypes.data),
+                                                        L0.scale, len(present), C.byref(plan)), 'snet_layer0_plan_create')
+            slot = np.zeros(ns, np.int32)
+            slot[list(present)] = np.arange(len(present), dtype=np.int32)
+            self.l0_plans[present] = (plan, torch.from_numpy(slot).to(self.dev), len(present))
+        return self.l0_plans[present]
+
+    def _layer0_bwd(self, c, g_m, h2, h2d, g_vec):
+        """layer 0's reverse pass: g_vec += the spherical and the radial part of every edge, from Bm = g_m B^T per atom"""
+        g, (plan, slot, _) = c.g, c.l0
+        scratch = self._new(int(self.lib.snet_layer0_scratch_size(plan, c.N)))
+        with _Span(self, 'conv_bwd_l0'):
+            _lib.check(self.lib.snet_layer0_conv_bwd(plan, _ptr(g_m), _ptr(h2), _ptr(h2d), _ptr(c.w_row), _ptr(g.row_ptr), _ptr(g.src),
+                                                     _ptr(g.types), _ptr(slot), _ptr(c.sh), _ptr(c.dsh), _ptr(g.edge_vec), c.N,
+                                                     _ptr(scratch), _ptr(g_vec), c.st), 'snet_layer0_conv_bwd')
+
     # -------------------------------------------------------------- compute
     def compute(self, g: Graph, halo=None, want_atomic_virial: bool = False, keep: bool = False):
         """Energy, per-atom energies, dE/d(edge_vec), forces and virial for one graph.
@@ -657,6 +710,7 @@ class HipForceEngine:
         side = None
         w_ready = {}
         any_fused = any(L.fused_fwd or L.fused_bwd for L in self.layers)
+        l0 = self._layer0_plan(g)   # layer 0's reverse pass from per-atom products: it reads h2' like a tangent-mode layer
         if E > 0:   # work lists of the fused reverse kernels (the topology's only device sync: built once per Graph)
             for L in self.layers:
                 if L.fused_bwd:
@@ -701,7 +755,7 @@ class HipForceEngine:
         h2_of = {t_: self._new(h2_rows, 64) for t_, L_ in enumerate(self.layers) if L_.fused_fwd or L_.fused_bwd}
         # layers whose reverse kernel runs in tangent mode also get h2' = d h2 / d|r| per row, from the same launch: the radial branch
         # is a function of |r| alone, so dE/d|r_e| = sum_k g_w[e, k] (h2' W2)[k] needs no reverse pass through the radial MLP
-        h2d_of = {t_: self._new(h2_rows, 64) for t_, L_ in enumerate(self.layers) if L_.tangent}
+        h2d_of = {t_: self._new(h2_rows, 64) for t_, L_ in enumerate(self.layers) if L_.tangent or (t_ == 0 and l0 is not None)}
         with _Span(self, 'radial_mlp_hidden_fwd'):
             demb = None
             if h2d_of:
@@ -724,7 +778,7 @@ class HipForceEngine:
         return SimpleNamespace(g=g, halo=halo, keep=keep, st=st, N=N, NT=NT, E=E, nb=nb, nsh=nsh, inter=inter, emb=emb, sh=sh, dsh=dsh,
                                pairs=pairs, w_row=w_row, emb_p=emb_p if pairs else None, side=side, w_ready=w_ready,
                                gw_bufs=gw_bufs if side is not None else None, gw_done=gw_done if side is not None else None,
-                               x=x, saved=saved, split=split, h2_of=h2_of, h2d_of=h2d_of)
+                               x=x, saved=saved, split=split, h2_of=h2_of, h2d_of=h2d_of, l0=l0)
 
     def _forward_layers(self, c):
         """the interaction layers (interaction_blocks.py:41-76): SI1, ghost exchange, self-connection, convolution, SI2, gate"""
@@ -889,14 +943,14 @@ class HipForceEngine:
         sh_T = None   # spherical harmonics in source-grouped edge order (transposed scalar convolution)
         g_vec = torch.zeros(E, 3, dtype=torch.float32, device=self.dev)  # spherical part, all layers
         # layers in tangent mode put their radial gradient into g_vec themselves; g_emb exists for the others only
-        need_g_emb = any(not L_.tangent for L_ in self.layers)
+        need_g_emb = any(not (L_.tangent or (t_ == 0 and c.l0 is not None)) for t_, L_ in enumerate(self.layers))
         g_emb = torch.zeros(E, nb, dtype=torch.float32, device=self.dev) if need_g_emb else None
         # fp16 operands of the fused reverse kernels: row maxima of the source rows and of the incoming gradient bound every
         # edge's g_w, from which the kernel derives that edge's power-of-two scale (no overflow possible).  The source-row
         # bounds of ALL layers come from one launch here (the rows have been complete since the forward pass).
         x_max_of = {}
         if self.fused_terms == 4 and E > 0:
-            ts = [t_ for t_, L_ in enumerate(self.layers) if L_.fused_bwd]
+            ts = [t_ for t_, L_ in enumerate(self.layers) if L_.fused_bwd and not (t_ == 0 and c.l0 is not None)]
             for t_ in ts:
                 x_max_of[t_] = self._new(NT)
             with _Span(self, 'row_bounds'):
@@ -911,10 +965,12 @@ class HipForceEngine:
             L = self.layers[t]
             ls = L.spec
             h, w, zs, y, h2 = saved[t]
+            l0 = c.l0 if t == 0 else None   # layer 0 from per-atom products: no fp16 operand, hence no bounds; radial part like tangent mode
+            tangent = L.tangent or l0 is not None
             g_y = self._new(N, ls.gate.irreps_in.dim)
             # fp16 operands of the fused reverse kernel: row bound of g_m = SI2^T g_y through the narrower g_y and SI2's
             # largest row norm (Cauchy-Schwarz), taken while the gate's reverse pass has the row in registers
-            g_max = self._new(N) if (L.fused_bwd and self.fused_terms == 4 and E > 0) else None
+            g_max = self._new(N) if (L.fused_bwd and self.fused_terms == 4 and E > 0 and l0 is None) else None
             with _Span(self, 'gate_bwd'):
                 _lib.check(lib.snet_gate_bwd_norm(_ptr(y), _ptr(g_x), _ptr(g_y), N, ls.gate.irreps_in.dim, ls.gate.irreps_out.dim,
                                                   L.gate_segs, len(ls.gate.segs), L.si2.t_norm if g_max is not None else 0.0,
@@ -958,7 +1014,6 @@ class HipForceEngine:
                                    'snet_segment_sum_rows')
 
             if L.fused_bwd:
-                tangent = L.tangent
                 g_h2 = None if (L.mlp_tail or tangent) else self._new(E, 64)
                 x_max = x_max_of.pop(t, None)   # (computed before the layer loop)
                 h2d = c.h2d_of.pop(t, None)
@@ -993,6 +1048,8 @@ class HipForceEngine:
                     else:
                         bwd_tiles(tpi, tni, nti)
                     gh_rows(0, N)
+                elif l0 is not None:
+                    self._layer0_bwd(c, g_m, h2, h2d, g_vec)
                 elif E > 0:
                     bwd_tiles(*g.tiles(L.tile_mode))
             else:
@@ -1017,7 +1074,7 @@ class HipForceEngine:
                         else:
                             halo.reverse(g_h, N)
             del g_xe
-            if L.fused_bwd and (L.mlp_tail or L.tangent):
+            if L.fused_bwd and (L.mlp_tail or tangent):
                 pass
             elif L.fused_bwd:
                 with _Span(self, 'radial_mlp_hidden_bwd'):

@@ -263,6 +263,30 @@ class ConvSpec:
         return hashlib.sha1(self.key.encode()).hexdigest()[:12]
 
 
+def layer0_moments_eligible(conv: ConvSpec, mlp_dims) -> bool:
+    """May a species-only first layer of this shape run from per-atom radial moments (csrc/snet_layer0.hip)?  Scalar inputs of one
+    multiplicity, one path (0, l -> l) per l = 0 .. lmax in l order with unit diagonal coupling, output blocks [path][m][channel],
+    radial dims [nb, 64, 64, wn]: what snet_layer0_plan_create's dimension checks cannot see, the caller checks here."""
+    from .irreps import cg_nonzeros
+    if len(conv.irreps_x) != 1 or conv.irreps_x[0][1] != 0:
+        return False
+    mul = conv.irreps_x[0][0]
+    if mul % 16 or not 16 <= mul <= 512 or len(mlp_dims) != 4 or tuple(mlp_dims[1:3]) != (64, 64):
+        return False
+    lmax = len(conv.paths) - 1
+    if not 0 <= lmax <= 3 or conv.irreps_sh.dim != (lmax + 1) ** 2 or conv.weight_numel != (lmax + 1) * mul or mlp_dims[3] != conv.weight_numel:
+        return False
+    for l, p in enumerate(conv.paths):
+        if (p.l1, p.l2, p.l3, p.mul, p.out_mul, p.out_ch) != (0, l, l, mul, mul, 0):
+            return False
+        if (p.w_off, p.x_off, p.sh_off, p.out_off) != (l * mul, 0, l * l, l * l * mul):
+            return False
+        terms = sorted((a, b, c, v * math.sqrt(2 * l + 1)) for a, b, c, v in cg_nonzeros(0, l, l))
+        if [(a, b, c) for a, b, c, _ in terms] != [(0, m, m) for m in range(2 * l + 1)] or any(abs(v - 1.0) > 1e-12 for *_, v in terms):
+            return False
+    return conv.irreps_out.dim == (lmax + 1) ** 2 * mul
+
+
 def transposed_scalar_conv(conv: ConvSpec):
     """Source-row gradient of a convolution whose outputs are all scalars (the last interaction layer of every NequIP-style
     model: paths (l, l -> 0) only), as a FORWARD convolution over the edges grouped by SOURCE atom:

@@ -27,24 +27,19 @@ class _DevRows:
 
 
 class NativeModel:
-    def __init__(self, model, state_dict: Optional[Dict[str, np.ndarray]] = None, device='cuda:0', modal=None):
+    def __init__(self, model, state_dict: Optional[Dict[str, np.ndarray]] = None, device='cuda:0', modal=None, layer0_moments: Optional[bool] = None):
         """model: path of a `.snet` file, or a reference config dict (then `state_dict` is required and
-        the file is written to a temporary location first)."""
+        the file is written to a temporary location first).
+        layer0_moments: HipForceEngine's switch (snet_model_set_layer0_moments); None = the sequencer's default (on, unless
+        SNET_LAYER0_MOMENTS=0 is in the environment)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError('NativeModel needs a ROCm GPU (no CPU fallback exists)')
         self.dev = torch.device(device)
         self.handle = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            if isinstance(model, dict):
-                if state_dict is None:
-                    raise ValueError('state_dict is required with a config dict')
-                with tempfile.TemporaryDirectory() as td:
-                    path = os.path.join(td, 'model.snet')
-                    write_model_file(path, model, state_dict, modal=modal)
-                    _lib.check(self.lib.snet_model_load(path.encode(), C.byref(self.handle)), 'snet_model_load')
-            else:
-                _lib.check(self.lib.snet_model_load(os.fspath(model).encode(), C.byref(self.handle)), 'snet_model_load')
+        self._load(model, state_dict, modal)
+        if layer0_moments is not None:
+            _lib.check(self.lib.snet_model_set_layer0_moments(self.handle, int(bool(layer0_moments))), 'snet_model_set_layer0_moments')
         cut, ns, nl = C.c_float(), C.c_int32(), C.c_int32()
         comm = (C.c_int32 * 64)()
         _lib.check(self.lib.snet_model_info(self.handle, C.byref(cut), C.byref(ns), C.byref(nl), comm, 64),
@@ -56,6 +51,18 @@ class NativeModel:
         # are immutable device tensors, so "same object" = "same topology"
         _lib.check(self.lib.snet_model_set_topology_cache(self.handle, 1), 'snet_model_set_topology_cache')
         self._last_graph = None
+
+    def _load(self, model, state_dict, modal):
+        with torch.cuda.device(self.dev):
+            if isinstance(model, dict):
+                if state_dict is None:
+                    raise ValueError('state_dict is required with a config dict')
+                with tempfile.TemporaryDirectory() as td:
+                    path = os.path.join(td, 'model.snet')
+                    write_model_file(path, model, state_dict, modal=modal)
+                    _lib.check(self.lib.snet_model_load(path.encode(), C.byref(self.handle)), 'snet_model_load')
+            else:
+                _lib.check(self.lib.snet_model_load(os.fspath(model).encode(), C.byref(self.handle)), 'snet_model_load')
 
     def eval_syncs(self) -> int:
         """stream synchronisations snet_model_eval has issued so far (0 per step once the topology is cached)"""
