@@ -555,6 +555,42 @@ int snet_mdb_step(double *pos, double *vel, const float *forces, const double *f
 int snet_mdb_init_velocities(double *vel, const double *mass, int64_t n_atoms, const int32_t *seg_ptr, const int32_t *sys_id,
                              int32_t n_sys, const double *kT, uint64_t seed, int32_t remove_com, void *stream);
 
+/* ---- batched isotropic NPT MD step (the cell moves on the device) --------------------------------
+ * snet_mdb_step with the stochastic cell rescaling of Bernetti and Bussi, J. Chem. Phys. 153, 114107 (2020), isotropic form: a
+ * barostat of first order in the cell, one normal deviate per system and step, no barostat momentum.  Arrays, units, phase bits
+ * and the thermostat's noise as snet_mdb_step, and per system: cell (fp64 [n_sys,9], row-major lattice vectors, updated in
+ * place), virial (fp64 [n_sys,6], the engine's virial_per_system: order xx,yy,zz,xy,yz,zx, stress = -virial / volume;
+ * virial_extra, fp64 [n_sys,6] or NULL, is added to it), p0 (fp64, the external pressure, eV/A^3), beta_over_tau (fp64, the
+ * isothermal compressibility over the barostat's relaxation time, A^3/(eV fs)), volume and pressure (fp64, out), active (int32,
+ * in/out: 1 while the system runs) and status (int32: the caller's 0, 2 written when the guard below fails).  With F and W the
+ * summed forces and virials at the current positions and cell, for every system with active == 1:
+ *   1. if phase & 1 (FINISH):  v += (dt/2) ACC F / m
+ *   2. K = sum_i (1/2) m_i |v_i|^2 / ACC;  V = |det cell|;  P = (2 K + W_xx + W_yy + W_zz) / (3 V)
+ *      e_kin[s] = K, volume[s] = V, pressure[s] = P                                       (always, in every phase)
+ *   3. if phase & 2 (START):   v += (dt/2) ACC F / m, then the barostat step S:
+ *        de = -beta_over_tau[s] (p0[s] - P) dt + sqrt(2 kT[s] beta_over_tau[s] dt / V) xi_s
+ *        mu = exp(de / 3);  x <- mu x;  v <- v / mu;  cell <- mu cell
+ *   4. then, still under START, the A-O-A part of snet_mdb_step:  c2 == 0:  x += dt v
+ *        else:  x += (dt/2) v;  v = c1 v + c2 sqrt(kT[s] ACC / m) xi;  x += (dt/2) v;           step_index[s] += 1
+ * S sits after both kicks with the forces of step k and before the next force evaluation: every kick uses forces at the positions
+ * and the cell they were evaluated at, and P is synchronous at step k.  xi_s is the first normal of the generator of
+ * snet_mdb_step under the counter (0, sys_id[s], step_index[s], tag 2): the same barostat noise alone as in a batch.  With
+ * kT == 0 or beta_over_tau == 0 the noise term is zero and no random number is generated for it; with beta_over_tau == 0 mu is
+ * exactly 1 and pos, vel, e_kin and step_index are those of snet_mdb_step bit for bit.
+ * Guard: nothing of a system but e_kin, volume and pressure is written before its next cell has passed.  If de or an entry of
+ * the new cell is not finite (a NaN virial), |de| > max_log_volume_step, or a face-to-face height of the new cell is below
+ * min_height (the batched neighbour kernels take heights down to cutoff / 64): active = 0, status = 2, and pos, vel, cell and
+ * step_index keep their bits -- the finishing kick of this launch is not stored either.  A system with active == 0 is taken at
+ * phase 0 in every later launch: its e_kin (of the velocities as they are), volume and pressure are written, nothing else.
+ * One 256-thread workgroup per system, fp64 sums in a fixed order, no atomics: two runs give identical bits, and a system's
+ * results do not depend on the other systems of the launch.                                                                   */
+int snet_mdb_npt_step(double *pos, double *vel, double *cell, const float *forces, const double *forces_extra, const double *virial,
+                      const double *virial_extra, const double *mass, int64_t n_atoms, const int32_t *seg_ptr,
+                      const int32_t *sys_id, int32_t n_sys, const double *kT, const double *p0, const double *beta_over_tau,
+                      int32_t *step_index, double *e_kin, double *volume, double *pressure, int32_t *active, int32_t *status,
+                      double dt, double c1, double c2, uint64_t seed, int32_t phase, double max_log_volume_step, double min_height,
+                      void *stream);
+
 /* ---- whole-model sequencer ------------------------------------------------------------------
  * replaces, for a native (C++) host, `model.forward(input_dict)` + `torch::autograd::grad(...)` of
  * the LAMMPS pair styles (sevenn/pair_e3gnn/pair_e3gnn.cpp:200-207, pair_e3gnn_parallel.cpp:424-503)

@@ -70,7 +70,8 @@ class ManyAtomsMixin:
     def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
         """`md_many` over ASE-like objects (get_atomic_numbers / get_positions / get_masses / get_cell / get_pbc, and
         get_velocities where the object has velocities): positions and velocities are written back with `set_positions` /
-        `set_velocities`.  Velocities at this surface are in A/fs, read and written as they are.  ASE's own time unit is
+        `set_velocities`; with `pressure=` (constant-pressure MD) the cell first, with `set_cell(cell, scale_atoms=False)`.
+        Velocities at this surface are in A/fs, read and written as they are.  ASE's own time unit is
         A sqrt(amu / eV) = 10.1805 fs, so the velocities of a real ase.Atoms are in A / (10.1805 fs): multiply
         get_velocities() by ase.units.fs (0.0982269) on the way in and divide by it on the way out, or pass
         `velocities=` in A/fs yourself (it takes precedence over the objects').  Because the mistake would be silent, objects of
@@ -80,6 +81,8 @@ class ManyAtomsMixin:
         results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
                                **atoms_velocities(atoms_list, kw))
         for a, r in zip(atoms_list, results):
+            if kw.get('pressure') is not None:
+                a.set_cell(r['cell'], scale_atoms=False)
             a.set_positions(r['positions'])
             a.set_velocities(r['velocities'])
         return results

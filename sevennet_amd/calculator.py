@@ -311,7 +311,12 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         or per system), friction (1/fs; 0 = NVE), velocities (A/fs; None: drawn at `temperature`), seed, log_every,
         traj_every, remove_com, system_ids, extra (as md_batch).  One dict per system, in the given order: the keys of `compute` (the last
         engine call, at the returned positions) plus `positions`, `velocities`, `e_pot`, `e_kin`, `temperature` and, with
-        traj_every > 0, `trajectory`.  The call's counters are kept as `self.md_info`."""
+        traj_every > 0, `trajectory`.  The call's counters are kept as `self.md_info`.
+        With pressure= (eV/A^3, scalar or per system) the run is isotropic NPT by stochastic cell rescaling, the cells moving on
+        the GPU too: further kw compressibility (A^3/eV, required), barostat_time (fs, default 1000) and max_log_volume_step
+        (default 0.1); every system fully periodic with at most batch.BATCH_MAX_ATOMS atoms.  The dicts then gain `cell` [3,3]
+        (the keys of `compute` are those at the returned positions AND cell), `volume` and `pressure` over the logged steps and
+        `status`: 'ok' or 'cell_failed' (md_batch)."""
         from .md import md_batch
         if not len(numbers_list) == len(positions_list) == len(masses_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '

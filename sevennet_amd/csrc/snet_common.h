@@ -214,6 +214,22 @@ __device__ __forceinline__ void load_force(const float *__restrict__ forces, con
     for (int k = 0; k < 3; ++k) F[k] += forces_extra[3 * i + k];
   }
 }
+// 3x3 matrices, row-major (the kernels that move a cell: snet_relax_cell.hip, snet_mdnpt.hip)
+__device__ __forceinline__ double det3(const double *a) {
+  return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
+}
+// the smallest face-to-face height of the cell c: |det c| / |a_j x a_k| over the three axes
+__device__ __forceinline__ double min_height3(const double *c) {
+  const double vol = fabs(det3(c));
+  double h = INFINITY;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double *u = c + 3 * ((i + 1) % 3), *w = c + 3 * ((i + 2) % 3);
+    const double x = u[1] * w[2] - u[2] * w[1], y = u[2] * w[0] - u[0] * w[2], z = u[0] * w[1] - u[1] * w[0];
+    h = fmin(h, vol / sqrt(x * x + y * y + z * z));
+  }
+  return h;
+}
 
 // ---- cross-lane exchange at VALU speed (no LDS): gfx950 permlane swaps + DPP -------------------
 // a + b where the "low" lanes (bit 5 / bit 4 of the lane id clear) end up with a_self + a_partner

@@ -29,10 +29,9 @@ __device__ __forceinline__ double wave_max_d(double v) {
 using snet::block_sum;    // per-system sums in a fixed order (snet_common.h)
 using snet::load_force;   // fp32 forces + optional fp64 forces_extra, in fp64
 
-// 3x3 matrices, row-major
-__device__ __forceinline__ double det3(const double *a) {
-  return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
-}
+// 3x3 matrices, row-major (det3 and min_height3: snet_common.h)
+using snet::det3;
+using snet::min_height3;
 __device__ __forceinline__ void inv3(const double *a, double det, double *inv) {
   const double id = 1.0 / det;
   inv[0] = (a[4] * a[8] - a[5] * a[7]) * id;
@@ -60,18 +59,6 @@ __device__ __forceinline__ void row_mul(const double *x, const double *m, double
 __device__ __forceinline__ void row_mul_t(const double *x, const double *m, double *out) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) out[j] = x[0] * m[3 * j] + x[1] * m[3 * j + 1] + x[2] * m[3 * j + 2];
-}
-// the smallest face-to-face height of the cell c: |det c| / |a_j x a_k| over the three axes
-__device__ __forceinline__ double min_height3(const double *c) {
-  const double vol = fabs(det3(c));
-  double h = INFINITY;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double *u = c + 3 * ((i + 1) % 3), *w = c + 3 * ((i + 2) % 3);
-    const double x = u[1] * w[2] - u[2] * w[1], y = u[2] * w[0] - u[0] * w[2], z = u[0] * w[1] - u[1] * w[0];
-    h = fmin(h, vol / sqrt(x * x + y * y + z * z));
-  }
-  return h;
 }
 // FIRE's velocity update of one component: mixing (keep, push) as decided for the system, then v += dt g
 __device__ __forceinline__ double new_velocity(double v_old, double g, double keep, double push, double nF, double nV, double dt) {

@@ -420,14 +420,24 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         included), `e_kin`, `temperature` (and `trajectory`); the counters are kept as `self.md_info`.  d3_term as in
         `relax_many`: with 'host' the D3 batch is prepared on the host (this path copies the positions down and the D3 forces
         up once per step), with 'device' the D3 term stays on the device and the D3 share of the results is one
-        `compute_many` at the returned positions."""
+        `compute_many` at the returned positions.
+        pressure= (constant-pressure MD, SevenNetCalculator.md_many) needs d3_term='device', whose term carries a virial: the D3
+        virial then enters the barostat's pressure, and the D3 share of the results is evaluated at the returned cells.  With
+        'host' it raises ValueError."""
         self._check_d3_term(d3_term)
+        npt = kw.get('pressure') is not None
+        if npt and d3_term == 'host':
+            raise ValueError("pressure is not available with d3_term='host': that D3 term reaches the integrator through the `extra` "
+                             "contract, which carries forces and energies but no virial, so its share of the pressure is unknown "
+                             "(pass d3_term='device', whose term carries one)")
         snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), list(positions_list)
         term = self._d3_term(numbers_list, positions_list, cells, pbcs, d3_term)
         results = snet.md_many(numbers_list, positions_list, masses_list, cells, pbcs, dt, steps, extra=term, **kw)
         self.md_info = snet.md_info
         if d3_term == 'device':
-            return [self._sum(a, b) for a, b in zip(results, d3.compute_many(numbers_list, [r['positions'] for r in results], cells, pbcs))]
+            final_cells = np.stack([r['cell'] for r in results]) if npt else cells
+            return [self._sum(a, b) for a, b in zip(results, d3.compute_many(numbers_list, [r['positions'] for r in results],
+                                                                             final_cells, pbcs))]
         # the model's results and the D3 results of the last step's evaluations, both at the returned positions
         return [self._sum(a, D3Calculator._results(b)) for a, b in zip(results, term.last)]

@@ -1,4 +1,5 @@
-"""Batched NVE / Langevin molecular dynamics at fixed cells, the state on the device from the first step to the last.
+"""Batched NVE / Langevin molecular dynamics at fixed cells, and isotropic NPT: the state on the device from the first step to the
+last.
 
 `md_batch` integrates B structures at once: per step one batched neighbor build (sevennet_amd.batch), one engine call and one
 `snet_mdb_step` launch (csrc/snet_mdstep.hip: one workgroup per system, fp64, fixed summation order).  Positions, velocities,
@@ -11,7 +12,12 @@ The integrator is BAOAB (Leimkuhler, Matthews, Appl. Math. Res. Express 2013, 34
 rule), folded around the force call so that one launch finishes step k and begins step k + 1; with friction 0 it is velocity
 Verlet.  The noise is Philox4x32-10 counted by (atom within its system, system id, step): a system's trajectory does not
 depend on the batch it runs in.  The rule is written out in include/snet_hip.h (snet_mdb_step) and restated in fp64 numpy in
-tests/md_ref.py.  Units: eV, A, fs, amu, K."""
+tests/md_ref.py.  Units: eV, A, fs, amu, K.
+
+With a `pressure`, `md_batch` runs isotropic NPT (`md_npt_loop`): one `snet_mdb_npt_step` launch (csrc/snet_mdnpt.hip) per step
+adds the stochastic cell rescaling of Bernetti and Bussi (J. Chem. Phys. 153, 114107 (2020)) between the kicks and the drift, on
+the engine's per-system virial; the cells stay on the device, where the batched neighbor kernels read them.  That rule is
+written out in include/snet_hip.h (snet_mdb_npt_step) and restated in tests/md_npt_ref.py."""
 from __future__ import annotations
 
 import math
@@ -21,11 +27,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import BatchForces, _as_host, batch_results, system_of, validate_batch_inputs
+from .batch import _MAX_IMAGE_REACH, BatchForces, _as_host, batch_results, system_of, validate_batch_inputs
+from .relax import check_cell_relax_systems
 
 ACC = 9.648533212e-3    # eV / (A amu) in A / fs^2
 KB = 8.617333262e-5     # eV / K
 FINISH, START = 1, 2    # snet_mdb_step phase bits
+NPT_STATUS_NAMES = ('ok', None, 'cell_failed')   # by the status word of snet_mdb_npt_step (2: its guard refused a next cell)
 
 
 def langevin_coefficients(friction: float, dt: float) -> Tuple[float, float]:
@@ -143,6 +151,81 @@ def init_velocities(vel: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor
                                                         int(bool(remove_com)), _lib.stream()), 'snet_mdb_init_velocities')
 
 
+def _per_system(x, B: int, what: str, unit: str) -> np.ndarray:
+    """a scalar or one value per system -> fp64 [B]; ValueError where it is neither"""
+    try:
+        a = _as_host(x, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what} = {x!r}: a scalar or one value per system ({unit}) is required') from None
+    if a.ndim == 0:
+        a = np.full(B, float(a))
+    if a.shape != (B,):
+        raise ValueError(f'{what} of shape {a.shape}: a scalar or one value per system ({B}) is required')
+    return a.copy()
+
+
+def validate_npt_inputs(n_at: np.ndarray, cells: np.ndarray, pbcs: np.ndarray, cutoff: float, pressure, compressibility,
+                        barostat_time, max_log_volume_step, extra=None):
+    """Host checks of what the barostat of md_batch adds to `validate_md_inputs` -> (pressure fp64 [B] in eV/A^3,
+    compressibility / barostat_time fp64 [B] in A^3/(eV fs)).  ValueError names the system."""
+    B = len(n_at)
+    if compressibility is None:
+        raise ValueError('pressure given without compressibility: the barostat needs the isothermal compressibility (A^3/eV) '
+                         'that sets its coupling')
+    p0 = _per_system(pressure, B, 'pressure', 'eV/A^3')
+    bad = ~np.isfinite(p0)
+    if bad.any():
+        b = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {b}: pressure = {p0[b]} eV/A^3, a finite pressure is required')
+    beta = _per_system(compressibility, B, 'compressibility', 'A^3/eV')
+    bad = ~((beta > 0) & np.isfinite(beta))
+    if bad.any():
+        b = int(np.nonzero(bad)[0][0])
+        raise ValueError(f'system {b}: compressibility = {beta[b]} A^3/eV, a finite compressibility > 0 is required')
+    real = (int, float, np.floating, np.integer)
+    for name, v in (('barostat_time', barostat_time), ('max_log_volume_step', max_log_volume_step)):
+        if isinstance(v, bool) or not isinstance(v, real) or not (v > 0 and math.isfinite(v)):
+            raise ValueError(f'{name} = {v!r}: a finite value > 0 is required')
+    if extra is not None and not getattr(extra, 'provides_virial', False):
+        raise ValueError('pressure with extra: the contract of `extra` carries forces and energies but no virial, so the '
+                         'pressure of the extra term is unknown (an extra marked `provides_virial = True` returns one; for D3 that is '
+                         "d3.D3DeviceTerm, SevenNetD3Calculator.md_many(d3_term='device'))")
+    try:
+        check_cell_relax_systems(n_at, cells, pbcs, cutoff)
+    except ValueError as e:   # (the same restrictions, named for this driver)
+        raise ValueError(str(e).replace('relax_cell', 'md with a pressure')) from None
+    return p0, beta / float(barostat_time)
+
+
+def md_npt_step(pos: torch.Tensor, vel: torch.Tensor, cell: torch.Tensor, forces: torch.Tensor, virial: torch.Tensor,
+                mass: torch.Tensor, seg_ptr: torch.Tensor, sys_id: torch.Tensor, kT: torch.Tensor, p0: torch.Tensor,
+                beta_over_tau: torch.Tensor, step_index: torch.Tensor, e_kin: torch.Tensor, volume: torch.Tensor,
+                pressure: torch.Tensor, active: torch.Tensor, status: torch.Tensor, dt: float, c1: float, c2: float, seed: int,
+                phase: int, max_log_volume_step: float, min_height: float, forces_extra: Optional[torch.Tensor] = None,
+                virial_extra: Optional[torch.Tensor] = None) -> None:
+    """one `snet_mdb_npt_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C ABI:
+    as `md_step`, and cell [B,9] / virial [B,6] / virial_extra [B,6] / p0 / beta_over_tau / volume / pressure fp64, active /
+    status int32)"""
+    N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
+    f64, i32 = torch.float64, torch.int32
+    want = [(pos, f64, (N, 3)), (vel, f64, (N, 3)), (cell, f64, (B, 9)), (forces, torch.float32, (N, 3)), (virial, f64, (B, 6)),
+            (mass, f64, (N,)), (seg_ptr, i32, (B + 1,)), (sys_id, i32, (B,)), (kT, f64, (B,)), (p0, f64, (B,)),
+            (beta_over_tau, f64, (B,)), (step_index, i32, (B,)), (e_kin, f64, (B,)), (volume, f64, (B,)), (pressure, f64, (B,)),
+            (active, i32, (B,)), (status, i32, (B,))]
+    if forces_extra is not None:
+        want.append((forces_extra, f64, (N, 3)))
+    if virial_extra is not None:
+        want.append((virial_extra, f64, (B, 6)))
+    _lib.check_device_tensors('md_npt_step', pos, want)
+    P = _lib.ptr
+    with torch.cuda.device(pos.device):
+        _lib.check(_lib.load().snet_mdb_npt_step(
+            P(pos), P(vel), P(cell), P(forces), P(forces_extra), P(virial), P(virial_extra), P(mass), N, P(seg_ptr), P(sys_id), B,
+            P(kT), P(p0), P(beta_over_tau), P(step_index), P(e_kin), P(volume), P(pressure), P(active), P(status), float(dt),
+            float(c1), float(c2), int(seed), int(phase), float(max_log_volume_step), float(min_height), _lib.stream()),
+            'snet_mdb_npt_step')
+
+
 def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray, *,
             dt: float, steps: int, friction: float, seed: int, log_every: int, traj_every: int, remove_com: bool,
             want_atomic_virial: bool):
@@ -185,6 +268,58 @@ def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.
     return g, out, dict(pos=pos, vel=vel, e_pot=e_pot_log, e_kin=e_kin_log, traj=traj, step_index=step_index), info
 
 
+def md_npt_loop(forces: BatchForces, positions, cells, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray,
+                p0: np.ndarray, beta_over_tau: np.ndarray, *, dt: float, steps: int, friction: float, seed: int, log_every: int,
+                traj_every: int, remove_com: bool, want_atomic_virial: bool, max_log_volume_step: float, min_height: float):
+    """`md_loop` at constant pressure: the force call reads the cells from the device (`cells_dev`), and one `snet_mdb_npt_step`
+    launch per step takes the engine's `virial_per_system` and `forces.virial_extra`.  cells [B,3,3]: the caller's, where the
+    run starts.  -> as `md_loop`, the state also with cell [B,9], volume and pressure [samples,B] and active / status [B]; nothing
+    is read back while the loop runs"""
+    dev = forces.engine.dev
+    n_atoms = forces.n_atoms
+    B, steps, log_every, traj_every = len(n_atoms), int(steps), int(log_every), int(traj_every)
+    c1, c2 = langevin_coefficients(friction, dt)
+    up = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a, dtype)).to(dev)  # noqa: E731
+    with torch.cuda.device(dev):
+        pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
+               else up(positions, np.float64)).reshape(-1, 3).clone()
+        N = int(pos.shape[0])
+        cell = up(np.asarray(cells, np.float64).reshape(B, 9), np.float64)
+        m_d, kT_d, id_d, seg = up(mass, np.float64), up(kT, np.float64), up(ids, np.int32), up(forces.a_ptr, np.int32)
+        p0_d, bt_d = up(p0, np.float64), up(beta_over_tau, np.float64)
+        if vel0 is None:
+            vel = torch.empty_like(pos)
+            init_velocities(vel, m_d, seg, id_d, kT_d, seed, remove_com)
+        else:
+            vel = up(vel0, np.float64)
+        step_index = torch.zeros(B, dtype=torch.int32, device=dev)
+        active = torch.ones(B, dtype=torch.int32, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        e_kin, volume, pressure = (torch.zeros(B, dtype=torch.float64, device=dev) for _ in range(3))
+        e_pot_log = torch.zeros(steps // log_every + 1, B, dtype=torch.float64, device=dev)
+        e_kin_log, volume_log, pressure_log = (torch.zeros_like(e_pot_log) for _ in range(3))
+        traj = torch.zeros(steps // traj_every + 1, N, 3, dtype=torch.float64, device=dev) if traj_every > 0 else None
+        g = out = None
+        for k in range(steps + 1):
+            last = k == steps
+            g, out, fx, ex = forces(pos, want_atomic_virial=want_atomic_virial and last, cells_dev=cell)
+            if traj is not None and k % traj_every == 0:
+                traj[k // traj_every].copy_(pos)
+            md_npt_step(pos, vel, cell, out['forces'], out['virial_per_system'], m_d, seg, id_d, kT_d, p0_d, bt_d, step_index, e_kin,
+                        volume, pressure, active, status, dt, c1, c2, seed, (FINISH if k > 0 else 0) | (0 if last else START),
+                        max_log_volume_step, min_height, fx, forces.virial_extra)
+            if k % log_every == 0:   # kinetic energy, volume and pressure of step k: v_k, and the cell the forces were evaluated at
+                j = k // log_every
+                e_pot_log[j].copy_(out['energy_per_system'] if ex is None else out['energy_per_system'] + ex)
+                e_kin_log[j].copy_(e_kin)
+                volume_log[j].copy_(volume)
+                pressure_log[j].copy_(pressure)
+    info = dict(n_force_calls=forces.n_force_calls, md_launches=steps + 1, system_steps_evaluated=forces.system_steps_evaluated)
+    state = dict(pos=pos, vel=vel, cell=cell, e_pot=e_pot_log, e_kin=e_kin_log, volume=volume_log, pressure=pressure_log, traj=traj,
+                 step_index=step_index, active=active, status=status)
+    return g, out, state, info
+
+
 def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms) -> List[Dict[str, Any]]:
     """`positions`, `velocities`, `e_pot`, `e_kin`, `temperature` (and `trajectory`) into each system's results dict: the one
     transfer to the host"""
@@ -201,11 +336,24 @@ def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms)
     return results
 
 
+def attach_npt(results: List[Dict[str, Any]], state: dict, cells_host: np.ndarray) -> List[Dict[str, Any]]:
+    """`cell`, `volume`, `pressure` and `status` of a constant-pressure run into each system's results dict"""
+    volume, pressure = state['volume'].cpu().numpy(), state['pressure'].cpu().numpy()
+    status = state['status'].cpu().numpy()
+    for b, res in enumerate(results):
+        res['cell'] = cells_host[b].copy()
+        res['volume'], res['pressure'] = volume[:, b].copy(), pressure[:, b].copy()
+        res['status'] = NPT_STATUS_NAMES[int(status[b])]
+    return results
+
+
 def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt: float, steps: int, temperature=None,
              friction: float = 0.0, velocities=None, seed: int = 0, log_every: int = 1, traj_every: int = 0, remove_com: bool = True,
              extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
-             system_ids=None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
-    """`steps` MD steps of `dt` fs for B structures at fixed cells: NVE (friction 0) or Langevin at `temperature`.
+             system_ids=None, pressure=None, compressibility=None, barostat_time: float = 1000.0,
+             max_log_volume_step: float = 0.1) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+    """`steps` MD steps of `dt` fs for B structures: NVE (friction 0) or Langevin at `temperature` at fixed cells, or with
+    `pressure` isotropic NPT, the cells moving on the device.
 
     engine: a HipForceEngine.  types / positions / cells / pbcs (and n_atoms for flat arrays) as `build_batch_graph`; masses (amu)
     and velocities (A/fs) per system or flat like the positions; the caller's arrays are not modified.  temperature (K): a
@@ -225,11 +373,36 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     the returned positions, plus `positions` and `velocities` [n,3] fp64, `e_pot`, `e_kin` (eV) and `temperature`
     (2 e_kin / (3 n KB), K) over the logged steps -- sample j belongs to step j log_every -- and `trajectory` [frames,n,3]
     (step j traj_every) when traj_every > 0.  info: n_force_calls == md_launches == steps + 1, system_steps_evaluated ==
-    B (steps + 1).  Invalid input raises ValueError before any device work."""
+    B (steps + 1).  Invalid input raises ValueError before any device work.
+
+    pressure (eV/A^3, a scalar or one value per system; None: fixed cells, the path above bit for bit): constant-pressure MD by
+    stochastic cell rescaling (Bernetti, Bussi, J. Chem. Phys. 153, 114107 (2020), isotropic; include/snet_hip.h,
+    snet_mdb_npt_step): each step scales cell, positions and inverse velocities by exp(de / 3), de = -(compressibility /
+    barostat_time) (pressure - P) dt + sqrt(2 kT compressibility dt / (V barostat_time)) xi, P = (2 e_kin + tr virial) / (3 V)
+    the instantaneous pressure at that step.  compressibility (A^3/eV, > 0, required; a scalar or one value per system): the
+    isothermal compressibility the coupling is scaled by -- an estimate is enough, it sets the relaxation time only;
+    barostat_time (fs).  Without a temperature (kT = 0) the noise term vanishes and the cell relaxes deterministically.  Every
+    system must be periodic along all three axes and one of the batched neighbor kernel (at most batch.BATCH_MAX_ATOMS atoms,
+    no height below cutoff / 64); a plain `extra` is refused, one marked `provides_virial = True` adds its virial to P.  The
+    results gain `cell` [3,3] fp64 (energy, forces and stress are those at the returned positions AND cell), `volume` (A^3) and
+    `pressure` (eV/A^3) over the logged steps, and `status`: 'ok', or 'cell_failed' where the step kernel refused a next cell
+    (de not finite -- a NaN virial --, |de| > max_log_volume_step, or a height below cutoff / 64): that system is returned as it
+    was before that step and stays in the batch, measured and not moved."""
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
     mass, vel0, kT, ids = validate_md_inputs(masses, n_at, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
                                              system_ids)
+    if pressure is not None:
+        p0, beta_over_tau = validate_npt_inputs(n_at, cells, pbcs, cutoff, pressure, compressibility, barostat_time,
+                                                max_log_volume_step, extra)
+        forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
+        g, out, state, info = md_npt_loop(forces, positions, cells, mass, vel0, kT, ids, p0, beta_over_tau, dt=dt, steps=steps,
+                                          friction=friction, seed=seed, log_every=log_every, traj_every=traj_every,
+                                          remove_com=remove_com, want_atomic_virial=want_atomic_virial,
+                                          max_log_volume_step=max_log_volume_step, min_height=cutoff / _MAX_IMAGE_REACH)
+        cells_h = state['cell'].cpu().numpy().reshape(-1, 3, 3)
+        results = attach_md(batch_results(g, out, cells_h, want_atomic_virial), state, g.seg_ptr_host, n_at)
+        return attach_npt(results, state, cells_h), info
     forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
     g, out, state, info = md_loop(forces, positions, mass, vel0, kT, ids, dt=dt, steps=steps, friction=friction, seed=seed,
                                   log_every=log_every, traj_every=traj_every, remove_com=remove_com,
