@@ -522,6 +522,43 @@ int snet_fire_cell_step(double *pos, double *vel, double *cell, double *vel_cell
                         double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain, int32_t constant_volume,
                         double min_height, void *stream);
 
+/* ---- batched nudged-elastic-band forces ----------------------------------------------------------
+ * The NEB forces of the moving images of n_bands bands in ONE launch: the improved tangent of Henkelman and Jonsson, J. Chem.
+ * Phys. 113, 9978 (2000), and the climbing image of Henkelman, Uberuaga and Jonsson, J. Chem. Phys. 113, 9901 (2000).  The flat
+ * arrays hold the INTERIOR images only: band b owns images [img_ptr[b], img_ptr[b+1]) (device int32 [n_bands+1]) of the n_img
+ * moving images, image j owns rows [seg_ptr[j], seg_ptr[j+1]) (device int32 [n_img+1]) of pos (fp64 [n_atoms,3]), forces (fp32
+ * [n_atoms,3]; forces_extra, fp64 [n_atoms,3] or NULL, is added in fp64), fixed (int32 [n_atoms] or NULL) and f_neb (fp64
+ * [n_atoms,3], written); all images of a band have the same n_b atoms in the same order.  energy (fp64 [n_img]; energy_extra,
+ * fp64 [n_img] or NULL, is added).  The two endpoints of band b are rows [end_ptr[b], end_ptr[b] + n_b) (initial) and the n_b
+ * rows after them (final) of pos_end (fp64 [n_end,3]; end_ptr device int32 [n_bands+1]), their energies e_end[2 b], e_end[2 b + 1]
+ * (fp64); the previous image of a band's first interior image is the initial endpoint, the next image of its last one the final
+ * endpoint.  Per band: cells and inv_cells (fp64 [n_bands,9], row-major lattice vectors with the zero rows of open axes padded to
+ * an invertible matrix, and its inverse), pbc (int32 [n_bands,3]), k (fp64 [n_bands], the spring constant), active and status
+ * (int32 [n_bands]), imax (int32 [n_bands], written).
+ * For every image i of a band with active == 1, in fp64, with R the positions, F the summed forces and E the summed energies:
+ *   F of an atom with fixed != 0 is zero before anything else, and so is its f_neb
+ *   mic(d):  s = d inv(cell);  s_k -= rint(s_k) on the periodic axes;  d = s cell  (row vectors; without a periodic axis d is
+ *            left as it is).  This is the shortest image whenever the true displacement is shorter than half the smallest
+ *            face-to-face height of the cell (|s_k| <= |d| / h_k): the documented domain, not checked.
+ *   t+ = mic(R_next - R_i),  t- = mic(R_i - R_prev);  Ep, Ei, Em the energies of the next, this and the previous image
+ *   Ep > Ei > Em: tau = t+;   Ep < Ei < Em: tau = t-;   otherwise, with dmax = max(|Ep - Ei|, |Em - Ei|) and dmin their min:
+ *   tau = t+ dmax + t- dmin if Ep > Em, else tau = t+ dmin + t- dmax (exact ties land here);  tau is then normalised over all
+ *   3 n_b components, a zero norm leaves tau = 0
+ *   f_neb = F - (F.tau) tau + k (|t+| - |t-|) tau
+ *   imax[b] = the interior image of highest energy (index within the band, lowest index on ties); with climb != 0 that image gets
+ *   f_neb = F - 2 (F.tau) tau instead, and no spring
+ * A band with active != 1 is skipped: its f_neb rows are written as zero, nothing else of it is touched.  If one of Ei, Ep, Em,
+ * |t+|^2, |t-|^2, |tau|^2 (before normalisation) or F.tau of an image is not finite, status[b] = 2 and active[b] = 0 are written
+ * (by every workgroup that finds it so) and that image's f_neb rows are zero: a snet_fire_step launch that follows leaves the
+ * band where it was.  Images of unequal size within a band, or endpoint rows outside pos_end, give status[b] = 3 the same way.
+ * One 256-thread workgroup per moving image, fp64 sums in a fixed order: two runs give identical bits.  With one segment per
+ * band (the bands' row offsets as its seg_ptr) snet_fire_step on f_neb is the single FIRE that ASE runs over NEB(images).  */
+int snet_neb_forces(const double *pos, const float *forces, const double *forces_extra, const double *energy,
+                    const double *energy_extra, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_img, const int32_t *img_ptr,
+                    int32_t n_bands, const double *pos_end, const int32_t *end_ptr, int64_t n_end, const double *e_end,
+                    const double *cells, const double *inv_cells, const int32_t *pbc, const int32_t *fixed, const double *k,
+                    int32_t climb, int32_t *active, int32_t *status, double *f_neb, int32_t *imax, void *stream);
+
 /* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
  * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
  * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of

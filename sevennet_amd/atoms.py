@@ -48,8 +48,9 @@ def atoms_velocities(atoms_list, kw: dict) -> dict:
 
 
 class ManyAtomsMixin:
-    """`calculate_many`, `relax_many_atoms` and `md_many_atoms` over ASE-like objects, for a class that has `compute_many`,
-    `relax_many` and `md_many` (a class without the latter two inherits adapters that fail where they are called)"""
+    """`calculate_many`, `relax_many_atoms`, `neb_many_atoms` and `md_many_atoms` over ASE-like objects, for a class that has
+    `compute_many`, `relax_many`, `neb_many` and `md_many` (a class without the latter three inherits adapters that fail where
+    they are called)"""
 
     def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
         """`compute_many` over ASE-like objects (anything with get_atomic_numbers / get_positions / get_cell / get_pbc)"""
@@ -65,6 +66,21 @@ class ManyAtomsMixin:
             if kw.get('relax_cell'):
                 a.set_cell(r['cell'], scale_atoms=False)
             a.set_positions(r['positions'])
+        return results
+
+    def neb_many_atoms(self, bands, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """`neb_many` over ASE-like objects: bands[b] is the list of a band's images (get_atomic_numbers / get_positions /
+        get_cell / get_pbc / set_positions), at least three.  Numbers, cell and pbc come from the band's first object; the
+        positions of the interior images are written back with `set_positions`, the endpoints are left untouched."""
+        bands = [list(band) for band in bands]
+        if any(len(band) == 0 for band in bands):
+            raise ValueError(f'band {[len(band) for band in bands].index(0)}: no images')
+        numbers, _, cells, pbcs = atoms_args([band[0] for band in bands])
+        results = self.neb_many(numbers, [np.stack([np.asarray(a.get_positions(), np.float64) for a in band]) for band in bands],
+                                cells, pbcs, fmax=fmax, steps=steps, **kw)
+        for band, r in zip(bands, results):
+            for a, image in zip(band[1:-1], r['images'][1:-1]):
+                a.set_positions(image['positions'])
         return results
 
     def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:

@@ -222,6 +222,7 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         self._z2type = np.full(120, -1, np.int64)  # sequential.py:80-83
         self.relax_info: Optional[Dict[str, int]] = None   # counters of the last relax_many call
         self.md_info: Optional[Dict[str, int]] = None      # counters of the last md_many call
+        self.neb_info: Optional[Dict[str, int]] = None     # counters of the last neb_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -302,6 +303,27 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         results, self.relax_info = relax_batch(self.model, self._types_list(numbers_list), list(positions_list), cells, pbcs,
                                                cutoff=self.cutoff, fmax=fmax, steps=steps,
                                                want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def neb_many(self, numbers_list, images_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
+        """Nudged elastic band relaxation of B bands at once (sevennet_amd.neb.neb_batch): numbers_list[b] the atomic numbers
+        [n_b] of band b, images_list[b] its images [M_b, n_b, 3] (M_b >= 3; the first and the last are the fixed endpoints,
+        neb.interpolate_band makes a starting band), cells[B,3,3], pbcs[B,3] (or one [3]) per band.  The moving images, their
+        velocities and the optimizer state stay on the GPU from the first step to the last: per step one batched evaluation of
+        all moving images, one launch that turns forces and energies into NEB forces (improved tangent, springs along it) and
+        one FIRE launch that moves all images of a band as one system, as ASE's FIRE(NEB(images)) does.  kw: k (spring constant
+        in eV/A^2, one or one per band; default 0.1), climb (climbing image), fixed_list (per band a bool mask or index list of
+        atoms that do not move, or None), repack_below, extra (must return energies too) and the FIRE parameters
+        (relax.FIRE_DEFAULTS).  Two-stage use is a second call with the first call's positions: a plain band first, then
+        climb=True.  One dict per band: `images` (M_b dicts with the keys of `compute` at the returned positions plus
+        `positions`, endpoints included), `converged`, `n_steps`, `status` ('converged', 'steps' or 'failed'), `neb_fmax`,
+        `imax` (index into `images`), `barrier` and `barrier_reverse` (eV).  The call's counters are kept as `self.neb_info`."""
+        from .neb import neb_batch
+        if len(numbers_list) != len(images_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(images_list)} bands')
+        results, self.neb_info = neb_batch(self.model, self._types_list(numbers_list), list(images_list), cells, pbcs,
+                                           cutoff=self.cutoff, fmax=fmax, steps=steps,
+                                           want_atomic_virial=self.compute_atomic_virial, **kw)
         return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:

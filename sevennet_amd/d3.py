@@ -350,6 +350,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
             self.calcs = list(pair)
         self.relax_info = None   # counters of the last relax_many call
         self.md_info = None      # counters of the last md_many call
+        self.neb_info = None     # counters of the last neb_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -412,6 +413,36 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         final_cells = np.stack([r['cell'] for r in results]) if kw.get('relax_cell') else cells
         at_final = d3.compute_many(numbers_list, [r['positions'] for r in results], final_cells, pbcs)
         return [self._sum(a, b) for a, b in zip(results, at_final)]
+
+    def neb_many(self, numbers_list, images_list, cells, pbcs, fmax: float = 0.05, steps: int = 500, d3_term: str = 'host',
+                 **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.neb_many` on the sum of the model's and the D3 forces and energies (sevennet_amd.neb): one dict
+        per band as there, the image dicts with the summed keys of `compute` at the returned positions; the tangents, `neb_fmax`,
+        `imax` and the barriers are those of model + D3.  The counters are kept as `self.neb_info`.  d3_term as in `relax_many`:
+        'host' prepares the D3 batch of all moving images on the host each step, 'device' keeps the term on the device; both
+        hand the band their energies."""
+        self._check_d3_term(d3_term)
+        snet, d3 = self.calcs
+        numbers_list, images_list = list(numbers_list), [np.asarray(im, np.float64) for im in images_list]
+        if len(numbers_list) != len(images_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(images_list)} bands')
+        for b, im in enumerate(images_list):
+            if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 3 or im.shape[1] != len(np.asarray(numbers_list[b]).reshape(-1)):
+                raise ValueError(f'band {b}: images of shape [M >= 3, {len(np.asarray(numbers_list[b]).reshape(-1))}, 3] are required, '
+                                 f'got {im.shape}')
+        # the flattened list of all images, band after band: what the `extra` of neb_batch is called over
+        band_of = np.repeat(np.arange(len(images_list)), [im.shape[0] for im in images_list])
+        cells_img = np.asarray(cells, np.float64).reshape(-1, 3, 3)[band_of]
+        pbcs_img = np.broadcast_to(np.asarray(pbcs, bool).reshape(-1, 3), (len(images_list), 3))[band_of]
+        flat_numbers = [np.asarray(numbers_list[b]).reshape(-1) for b in band_of]
+        term = self._d3_term(flat_numbers, [x for im in images_list for x in im], cells_img, pbcs_img, d3_term)
+        results = snet.neb_many(numbers_list, images_list, cells, pbcs, fmax=fmax, steps=steps, extra=term, **kw)
+        self.neb_info = snet.neb_info
+        at_final = d3.compute_many(flat_numbers, [x['positions'] for r in results for x in r['images']], cells_img, pbcs_img)
+        it = iter(at_final)
+        for r in results:
+            r['images'] = [self._sum(a, next(it)) for a in r['images']]
+        return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, d3_term: str = 'host',
                 **kw) -> List[Dict[str, Any]]:
