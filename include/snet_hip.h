@@ -290,6 +290,32 @@ int snet_layer0_conv_bwd(const snet_layer0_plan *plan, const float *g_out, const
                          const int32_t *row_ptr, const int32_t *src, const int32_t *types, const int32_t *species_slot,
                          const float *sh, const float *dsh, const float *edge_vec, int64_t n_nodes, float *scratch, float *g_vec,
                          void *stream);
+/* ---- scalar-output (last) interaction layer: the whole reverse pass in one source-grouped launch ------------------------------
+ * Every path is (l, l -> 0) with the diagonal coupling c_l, so g_h (d/d source row) and g_vec (d/d r_e) are derivatives of one
+ * bilinear form  B = scale sum_e sum_{l,u} g_out[center(e)][l,u] w_e[l,u] c_l sum_a x[src(e)][l,u,a] Y_e[l,a],  w_e = h2_e W2.
+ * A wave takes one SOURCE row j, keeps x[j] on chip and walks j's out-edges (col_ptr / snet_edges_by_source) in tiles of 16:
+ *   t_e = scale c_l w_e g_out[center(e)];  g_x[j][l,u,a] = sum_e t_e Y_e[l,a];  dB/dY_e[l,a] = sum_u t_e x[j][l,u,a];
+ *   dB/d|r_e| = sum_{l,u} scale c_l w'_e g_out[center(e)] sum_a x[j][l,u,a] Y_e[l,a],  w'_e = h2d_e W2
+ * -- one pair of W2 products per edge (two-term fp16 operands, fp32 accumulate) where snet_conv_bwd_fused_tangent +
+ * snet_conv_fwd_fused of the transposed shape run two, no dx-float gather per edge, no operand that depends on g_out (hence no
+ * x_rowmax / g_rowmax).  g_vec[eperm[e']] is ADDED to (plain read-modify-write: an edge has one source); g_x rows [row_a, row_b)
+ * are WRITTEN whole, the dead ranges of snet_conv_plan_transposed as zeros.  Fixed summation order: two launches give the same bits,
+ * and a call over [a, b) then [b, c) the bits of one over [a, c).
+ *   plan     conv = the layer's shape: refused unless its transposed product exists, its column factors are 1 / sqrt(2 l + 1) in
+ *            runs of multiples of 16 for l = 0, 1, .. <= 3 (one path (l, l -> 0) per l, in l order: the CALLER vouches for the diagonal
+ *            coupling and for the x blocks following each other in l order around the dead ranges --
+ *            sevennet_amd.model_spec.lastlayer_merged_eligible) and a kernel for these multiplicities is compiled in;
+ *            W2_host[64, wn] as the fused kernels take it (the column factors are applied here)
+ *   x, g_out, h2, h2d, sh[E,nsh], dsh[E,3 nsh], edge_vec[E,3]: as snet_conv_bwd_fused_tangent (sh / dsh / edge_vec / g_vec in the
+ *            destination-grouped edge order); col_ptr[n_total + 1], center_t, w_row_t, eperm: as snet_conv_fwd_fused of the
+ *            transposed shape takes them (col_ptr is NOT offset by row_a)                                                        */
+typedef struct snet_lastlayer_plan snet_lastlayer_plan;
+int snet_lastlayer_plan_create(const snet_conv_plan *conv, const float *W2_host, snet_lastlayer_plan **plan);
+void snet_lastlayer_plan_destroy(snet_lastlayer_plan *plan);
+int snet_lastlayer_conv_bwd(const snet_lastlayer_plan *plan, const float *x, const float *g_out, const float *sh, const float *dsh,
+                            const float *edge_vec, const float *h2, const float *h2d, const int32_t *col_ptr,
+                            const int32_t *center_t, const int32_t *w_row_t, const int32_t *eperm, int64_t row_a, int64_t row_b,
+                            float scale, float *g_x, float *g_vec, void *stream);
 /* g_xe[E,dx] of snet_conv_bwd_fused is an intermediate with its own row layout: the 16-channel chunks of a row are stored in
  * the order the kernel produces them ([x block][channel tile][component]: each (block, tile) writes one contiguous run per
  * edge instead of half cache lines).  chunk_pos[s] (dx / 16 entries, host) = position of standard chunk s in the row;
@@ -676,6 +702,11 @@ int snet_model_set_topology_cache(snet_model *model, int32_t enable);
  * load time) or through the fused kernel (0), where the model is eligible at all: its file carries the metadata key layer0_moments=1
  * and the shape passes snet_layer0_plan_create.  Applies to the following evaluations.  For A/B runs and tests. */
 int snet_model_set_layer0_moments(snet_model *model, int32_t enable);
+/* the last layer's reverse pass through snet_lastlayer_conv_bwd (enable != 0; the default unless SNET_LAST_LAYER_MERGED=0 is in the
+ * environment at load time) or through snet_conv_bwd_fused_tangent + the transposed convolution (0), where the model is eligible:
+ * its file carries the metadata key last_layer_merged=1 and the shape passes snet_lastlayer_plan_create.  Applies to the following
+ * evaluations.  For A/B runs and tests. */
+int snet_model_set_last_layer_merged(snet_model *model, int32_t enable);
 int snet_model_topology_changed(snet_model *model);
 int64_t snet_model_eval_syncs(const snet_model *model);
 int snet_model_set_halo(snet_model *model, snet_halo_fn forward, snet_halo_fn reverse, void *user,

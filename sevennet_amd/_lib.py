@@ -100,6 +100,11 @@ SIGNATURES = {
     'snet_layer0_scratch_size': (C.c_int64, [C.c_void_p, C.c_int64]),
     'snet_layer0_conv_bwd': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
                                        C.c_int64, c_f32p, c_f32p, c_stream]),
+    'snet_model_set_last_layer_merged': (C.c_int, [C.c_void_p, C.c_int32]),
+    'snet_lastlayer_plan_create': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    'snet_lastlayer_plan_destroy': (None, [C.c_void_p]),
+    'snet_lastlayer_conv_bwd': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p,
+                                          c_i32p, C.c_int64, C.c_int64, C.c_float, c_f32p, c_f32p, c_stream]),
     'snet_fused_plan_gxe_chunks': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     'snet_segment_sum_rows_chunked': (C.c_int, [c_f32p, c_i32p, c_i32p, C.c_int64, C.c_int32, c_i32p, c_f32p, c_stream]),
     'snet_edge_vectors': (C.c_int, [c_f64p, c_i32p, c_i32p, c_f64p, C.c_int64, c_f32p, c_stream]),

@@ -19,7 +19,7 @@ import sys
 from typing import List
 
 from . import codegen, codegen_fused
-from .shapes import aot_conv_specs
+from .shapes import aot_conv_specs, lastlayer_test_configs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
@@ -30,7 +30,7 @@ _sfx = ('_' + os.path.basename(LIB).replace('.so', '')) if os.environ.get('SNET_
 GEN = os.path.join(CSRC, 'generated' + _sfx)
 OBJ = os.path.join(CSRC, 'build' + _sfx)
 ARCH = 'gfx950'
-STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_md.hip', 'snet_d3.hip', 'snet_d3_ref.cpp']
+STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_lastlayer.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_md.hip', 'snet_d3.hip', 'snet_d3_ref.cpp']
 
 
 def _rocm_root() -> str:
@@ -149,7 +149,7 @@ def build(jobs: int = 0, force: bool = False, extra_configs=(), verbose: bool = 
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.join(CSRC, 'generated'), exist_ok=True)
     codegen.write_if_changed(os.path.join(CSRC, 'generated', 'sh_generated.h'), codegen.gen_sh_header(3))
-    specs = aot_conv_specs(extra_configs)
+    specs = aot_conv_specs(list(extra_configs) + list(lastlayer_test_configs().values()))   # (+ the test-only shapes)
     sources = [os.path.join(CSRC, s) for s in STATIC_SOURCES]
     keep = set()
     for tag, spec in specs.items():

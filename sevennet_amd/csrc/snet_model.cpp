@@ -133,6 +133,7 @@ struct Layer {
   snet_conv_plan *tconv = nullptr;
   snet_mlp_plan *tmlp = nullptr;
   snet_fused_plan *tfused = nullptr;
+  snet_lastlayer_plan *merged = nullptr;   // last layer: g_h and g_vec from one source-grouped launch (snet_lastlayer_conv_bwd)
   int tile_mode = 0;   // work list of the fused reverse kernel: 0 = per-row tiles, 1 = packed (snet_fused_plan_tile_mode)
   std::vector<int32_t> t_dead;       // (offset, length) column ranges of g_h it leaves unwritten
   Linear sc, si1, si2;
@@ -287,6 +288,12 @@ struct snet_model {
   // atoms (read back when the topology cache misses), at most 4 -- engine.py's rule, so that both hosts run the same launches.
   bool l0_mode = [] {
     const char *e = getenv("SNET_LAYER0_MOMENTS");
+    return e == nullptr || strcmp(e, "0") != 0;
+  }();
+  // The last layer's reverse pass in one launch (snet_lastlayer_conv_bwd, engine.py's `last_layer_merged`) where its Layer carries a
+  // plan; snet_model_set_last_layer_merged(0) or SNET_LAST_LAYER_MERGED=0 keep the tangent-mode kernel + the transposed convolution.
+  bool ll_mode = [] {
+    const char *e = getenv("SNET_LAST_LAYER_MERGED");
     return e == nullptr || strcmp(e, "0") != 0;
   }();
   bool l0_shape_ok = false;           // layer 0's shape and radial network are inside snet_layer0_plan_create's domain
@@ -494,6 +501,15 @@ extern "C" int snet_model_load_memory(const void *blob, int64_t n_bytes, snet_mo
       }
     }
   }
+  // The last layer's one-launch reverse pass: paths, offsets and coupling were checked where the file was written (metadata key
+  // last_layer_merged=1, model_spec.lastlayer_merged_eligible; a file without the key keeps the pair of kernels); the plan checks
+  // the dimensions and the column factors of the transposed product.
+  if (good && m->n_layers > 1 && ("\n" + m->meta).find("\nlast_layer_merged=1\n") != std::string::npos) {
+    Layer &LL = m->layers.back();
+    if (LL.fused && LL.tfused && m->fused_terms == 4 && LL.mlp[1] == 64 && LL.mlp[2] == 64 &&
+        snet_lastlayer_plan_create(LL.conv, snet::mlp_plan_w2_host(LL.mlp_plan), &LL.merged) != 0)
+      LL.merged = nullptr;
+  }
   } catch (const std::exception &e) {  // nothing may propagate through an extern "C" entry point
     snet::set_error(std::string("exception: ") + e.what());
     good = false;
@@ -545,6 +561,7 @@ extern "C" void snet_model_destroy(snet_model *m) {
   for (auto &L : m->layers) {
     snet_fused_plan_destroy(L.fused);
     snet_fused_plan_destroy(L.tfused);
+    snet_lastlayer_plan_destroy(L.merged);
     snet_radial_mlp_plan_destroy(L.tmlp);
     snet_conv_plan_destroy(L.tconv);
     if (L.gxe_chunks) (void)hipFree(L.gxe_chunks);
@@ -618,6 +635,12 @@ extern "C" int snet_model_set_interior(snet_model *m, int64_t n_interior) {
 extern "C" int snet_model_set_layer0_moments(snet_model *m, int32_t enable) {
   SNET_REQUIRE(m != nullptr, "snet_model_set_layer0_moments: null model");
   m->l0_mode = enable != 0;
+  return 0;
+}
+
+extern "C" int snet_model_set_last_layer_merged(snet_model *m, int32_t enable) {
+  SNET_REQUIRE(m != nullptr, "snet_model_set_last_layer_merged: null model");
+  m->ll_mode = enable != 0;
   return 0;
 }
 
@@ -709,11 +732,14 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   SNET_REQUIRE(!pairs || (pair_edge != nullptr && n_pairs > 0 && n_pairs <= E),
                "snet_model_eval: w_row needs pair_edge and 0 < n_pairs <= n_edges");
   const int64_t WR = pairs ? n_pairs : E;  // rows of each layer's radial-weight matrix
-  bool any_fused = false, any_transposed = false;
+  bool any_fused = false, any_transposed = false, need_sh_t = false;
   bool need_tiles[2] = {false, false};   // per work-list format of the fused reverse kernels
+  // the last layer's reverse pass as one source-grouped launch (its radial gradient from h2', like a tangent-mode layer)
+  const bool ll_on = m->ll_mode && m->layers.back().merged != nullptr;
   for (auto &L : m->layers) {
     any_fused |= L.fused != nullptr;
     any_transposed |= L.tfused != nullptr;
+    need_sh_t |= L.tfused != nullptr && !(ll_on && &L == &m->layers.back());   // (the merged launch reads sh through eperm)
     if (L.fused) need_tiles[L.tile_mode != 0] = true;
   }
   // the second stream only carries the separate radial-MLP kernels (same policy as engine.py)
@@ -829,7 +855,8 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   for (int t = 0; t < Lc; ++t) {
     saved[t].h = A.f((size_t)NT * m->layers[t].dx);
     saved[t].w = A.f(m->layers[t].fused ? (size_t)WR * 64 : (size_t)WR * m->layers[t].wn);
-    const bool tg = m->layers[t].fused != nullptr && (snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0 || (t == 0 && l0 != nullptr));
+    const bool tg = m->layers[t].fused != nullptr && (snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0 || (t == 0 && l0 != nullptr) ||
+                                                          (t == Lc - 1 && ll_on));
     saved[t].wd = tg ? A.f((size_t)WR * 64) : nullptr;
     all_tangent = all_tangent && tg;
     saved[t].y = A.f((size_t)N * m->layers[t].gin);
@@ -930,9 +957,9 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       center_t = reinterpret_cast<int32_t *>(A.f((size_t)E + 64));
       w_row_t = reinterpret_cast<int32_t *>(A.f((size_t)E + 64));
     }
-    sh_t = A.f((size_t)E * nsh + 64);
+    if (need_sh_t) sh_t = A.f((size_t)E * nsh + 64);
     if (!topo_hit && (rc = snet_edges_by_source(row_ptr, N, eperm, pairs ? w_row : nullptr, E, center_t, w_row_t, st))) return rc;
-    if ((rc = snet_gather_rows(sh, eperm, sh_t, E, nsh, st))) return rc;   // (the harmonics change with the positions: every step)
+    if (need_sh_t && (rc = snet_gather_rows(sh, eperm, sh_t, E, nsh, st))) return rc;   // (the harmonics change with the positions: every step)
   }
   int32_t *tile_ptr_b = nullptr;   // boundary rows' tiles: tile_node + k, tile pointers re-based by -k
   int64_t tile_k = 0;
@@ -1107,7 +1134,8 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     int32_t dims[8];
     int nj = 0;
     for (int t = 0; t <= Lc; ++t) {
-      if (t < Lc && m->layers[t].fused && !(t == 0 && l0 != nullptr)) {   // (snet_layer0_conv_bwd has no fp16 operand)
+      if (t < Lc && m->layers[t].fused && !(t == 0 && l0 != nullptr) &&   // (snet_layer0_conv_bwd has no fp16 operand,
+          !(t == Lc - 1 && ll_on && m->layers[t].tfused && t > 0)) {      //  snet_lastlayer_conv_bwd none that depends on g_m)
         x_max_of[t] = A.f((size_t)NT + 64);
         xs[nj] = saved[t].h; outs[nj] = x_max_of[t]; rows[nj] = NT; dims[nj] = m->layers[t].dx; ++nj;
       }
@@ -1123,7 +1151,8 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     A.off = mark2;
     float *g_y = A.f((size_t)N * L.gin);
     // fp16 operands of the fused reverse kernel: bound of every row of g_m = SI2^T g_y (Cauchy-Schwarz), taken in the same pass
-    float *g_max = (L.fused && E > 0 && m->fused_terms == 4 && !(t == 0 && l0 != nullptr)) ? A.f((size_t)N) : nullptr;
+    const bool merged = t > 0 && t == Lc - 1 && ll_on && L.tfused != nullptr && E > 0;
+    float *g_max = (L.fused && E > 0 && m->fused_terms == 4 && !(t == 0 && l0 != nullptr) && !merged) ? A.f((size_t)N) : nullptr;
     if ((rc = snet_gate_bwd_norm(saved[t].y, g_x, g_y, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(),
                                  g_max ? L.si2.t_norm : 0.f, g_max, st)))
       return rc;
@@ -1138,7 +1167,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       float *g_h2 = tail ? nullptr : A.f((size_t)E * 64);
       float *x_max = x_max_of[t];   // (bounds of every edge's g_w, see snet_row_absmax; computed before the layer loop)
       auto bwd_tiles = [&](const int32_t *tp, const int32_t *tn, int64_t nt) -> int {
-        if (E <= 0 || nt <= 0) return 0;
+        if (E <= 0 || nt <= 0 || merged) return 0;   // (merged: gh_rows adds to g_vec too)
         if (tg)
           return snet_conv_bwd_fused_tangent(L.fused, saved[t].h, sh, dsh, saved[t].w, saved[t].wd, pairs ? w_row : nullptr, row_ptr, src,
                                              tp, tn, nt, L.conv_scale, g_m, g_xe, edge_vec, g_vec, x_max, g_max, st);
@@ -1159,12 +1188,15 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         // source rows [a, b) of g_h: the transposed scalar convolution over the edges grouped by source, or the segment sum
         auto gh_rows = [&](int64_t a, int64_t b) -> int {
           if (b <= a) return 0;
+          if (merged)
+            return snet_lastlayer_conv_bwd(L.merged, saved[t].h, g_m, sh, dsh, edge_vec, saved[t].w, saved[t].wd, col_ptr, center_t,
+                                           w_row_t, eperm, a, b, L.conv_scale, g_h, g_vec, st);
           if (transposed)
             return snet_conv_fwd_fused(L.tfused, g_m, sh_t, saved[t].w, w_row_t, col_ptr + a, center_t, b - a, L.conv_scale,
                                        g_h + (size_t)a * L.dx, st);
           return snet_segment_sum_rows_chunked(g_xe, col_ptr + a, eperm, b - a, L.dx, L.gxe_chunks, g_h + (size_t)a * L.dx, st);
         };
-        if (transposed)
+        if (transposed && !merged)
           for (size_t i = 0; i + 1 < L.t_dead.size(); i += 2)
             SNET_REQUIRE(hipMemset2DAsync(g_h + L.t_dead[i], (size_t)L.dx * 4, 0, (size_t)L.t_dead[i + 1] * 4, (size_t)NT, st) ==
                              hipSuccess, "snet_model_eval: memset failed");

@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .model_spec import (ACT_CST, ACT_ID, LinearSpec, ModelSpec, build_model_spec, folded_readout, layer0_moments_eligible,
-                         linear_modal_bias, linear_weight_matrices, species_only_tables, transposed_scalar_conv)
+from .model_spec import (ACT_CST, ACT_ID, LinearSpec, ModelSpec, build_model_spec, folded_readout, lastlayer_merged_eligible,
+                         layer0_moments_eligible,                         linear_modal_bias, linear_weight_matrices, species_only_tables, transposed_scalar_conv)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -300,7 +300,8 @@ class HipForceEngine:
     def __init__(self, config: dict, state_dict: Dict[str, np.ndarray], device='cuda:0', mlp_mode: str = 'bf16x6',
                  linear_mode: str = 'bf16x6', fused='auto', fused_terms='f16x3', modal=None, overlap: bool = True,
                  mlp_tail: bool = True, transposed_conv: bool = True, species_tables: bool = True,
-                 fold_readout: bool = True, tangent: bool = True, layer0_moments: bool = True):
+                 fold_readout: bool = True, tangent: bool = True, layer0_moments: bool = True,
+                 last_layer_merged: bool = True):
         """mlp_mode / linear_mode: 'bf16x6' (split-precision MFMA, fp32-class accuracy, default) or
         'fp32' (exact fp32 MFMA) for the fused radial MLP / the node-level equivariant linears.
         fused: 'auto' (default) / True / False / 'fwd' / 'bwd' -- run the radial MLP's last layer INSIDE the
@@ -335,6 +336,9 @@ class HipForceEngine:
         modal: fidelity channel (name from config['_modal_map'] or index) of a multi-modal model; the
         one-hot inputs of its linears become constant biases, shift/scale rows are selected at load.
         layer0_moments: layer 0's reverse pass from one W2 product per atom (snet_layer0_conv_bwd); see _init_layer0.
+        last_layer_merged: the last layer's reverse pass (g_h and g_vec) in one source-grouped launch (snet_lastlayer_conv_bwd; DESIGN
+        4l) where model_spec.lastlayer_merged_eligible allows it; False keeps the tangent-mode reverse kernel + the transposed
+        convolution (A/B runs, the tests' reference).  The forward pass is the same either way.
         """
         self.fused_terms, self.fused_mode = self._check_modes(mlp_mode, linear_mode, fused, fused_terms)
         self.mlp_mode = mlp_mode
@@ -455,6 +459,7 @@ class HipForceEngine:
                     _lib.check(self.lib.snet_fused_plan_create(tpl, tmlp, self.fused_terms, C.byref(tfp)), 'snet_fused_plan_create')
                     L.tplan, L.tmlp, L.tconv = tfp, tmlp, tpl
                     L.t_dead = [(dead[2 * i], dead[2 * i + 1]) for i in range(nd.value)]
+                self._init_last_layer(L, len(sp.layers), last_layer_merged)
                 segs = (_lib.GateSeg * len(ls.gate.segs))()
                 inv_act = {v: k for k, v in ACT_ID.items()}
                 for i, s in enumerate(ls.gate.segs):
@@ -516,6 +521,8 @@ class HipForceEngine:
                     self.lib.snet_fused_plan_destroy(L.tplan)
                     self.lib.snet_conv_plan_destroy(L.tconv)
                     self.lib.snet_radial_mlp_plan_destroy(L.tmlp)
+                if getattr(L, 'mplan', None) is not None:
+                    self.lib.snet_lastlayer_plan_destroy(L.mplan)
                 self.lib.snet_conv_plan_destroy(L.plan)
                 if getattr(L, 'mlp_plan', None) is not None:
                     self.lib.snet_radial_mlp_plan_destroy(L.mlp_plan)
@@ -622,6 +629,19 @@ class HipForceEngine:
                 g = ga
 
     # ------------------------------------------------- layer 0 from moments
+    def _init_last_layer(self, L, n_layers, last_layer_merged):
+        """last_layer_merged: both gradients of the last layer (g_h, g_vec) from one source-grouped launch (snet_lastlayer_conv_bwd,
+        csrc/snet_lastlayer.hip) in place of the tangent-mode reverse kernel + the transposed convolution, which stay
+        as the fallback (L.tplan).  Such a layer takes its radial gradient from h2' like a tangent-mode layer."""
+        ls = L.spec
+        L.mplan = None
+        if (last_layer_merged and L.tplan is not None and ls.t == n_layers - 1 and L.fused_fwd and self.fused_terms == 4
+                and lastlayer_merged_eligible(ls.conv, ls.mlp_dims)):
+            mpl = C.c_void_p()
+            _lib.check(self.lib.snet_lastlayer_plan_create(L.plan, L.w2_host.ctypes.data_as(C.c_void_p), C.byref(mpl)),
+                       'snet_lastlayer_plan_create')
+            L.mplan, L.tangent = mpl, True
+
     def _init_layer0(self, layer0_moments):
         """layer0_moments: the reverse pass of the first interaction layer (species-only source rows, paths (0, l -> l)) from one
         grouped GEMM per atom and a pass over the edges instead of the fused per-edge kernel (snet_layer0_conv_bwd); the
@@ -950,7 +970,8 @@ class HipForceEngine:
         # bounds of ALL layers come from one launch here (the rows have been complete since the forward pass).
         x_max_of = {}
         if self.fused_terms == 4 and E > 0:
-            ts = [t_ for t_, L_ in enumerate(self.layers) if L_.fused_bwd and not (t_ == 0 and c.l0 is not None)]
+            ts = [t_ for t_, L_ in enumerate(self.layers)
+                  if L_.fused_bwd and not (t_ == 0 and c.l0 is not None) and L_.mplan is None]   # (neither has an fp16 operand to bound)
             for t_ in ts:
                 x_max_of[t_] = self._new(NT)
             with _Span(self, 'row_bounds'):
@@ -970,7 +991,7 @@ class HipForceEngine:
             g_y = self._new(N, ls.gate.irreps_in.dim)
             # fp16 operands of the fused reverse kernel: row bound of g_m = SI2^T g_y through the narrower g_y and SI2's
             # largest row norm (Cauchy-Schwarz), taken while the gate's reverse pass has the row in registers
-            g_max = self._new(N) if (L.fused_bwd and self.fused_terms == 4 and E > 0 and l0 is None) else None
+            g_max = self._new(N) if (L.fused_bwd and self.fused_terms == 4 and E > 0 and l0 is None and L.mplan is None) else None
             with _Span(self, 'gate_bwd'):
                 _lib.check(lib.snet_gate_bwd_norm(_ptr(y), _ptr(g_x), _ptr(g_y), N, ls.gate.irreps_in.dim, ls.gate.irreps_out.dim,
                                                   L.gate_segs, len(ls.gate.segs), L.si2.t_norm if g_max is not None else 0.0,
@@ -979,6 +1000,7 @@ class HipForceEngine:
                 g_m = self._linear_T(L.si2, g_y, N, g)
             # layer 0: inputs depend on species only -> no source-row gradient needed
             use_t = t > 0 and getattr(L, 'tplan', None) is not None and E > 0
+            use_m = use_t and L.mplan is not None   # g_h and g_vec of the layer from one launch per range of source rows
             g_xe = self._new(E, ls.si1.dim_out) if (t > 0 and not use_t) else None
             g_w = g_h2 = None
             # reverse split (t > 0, fused kernels): boundary tiles first -- they hold every edge with a ghost source --
@@ -988,9 +1010,9 @@ class HipForceEngine:
             g_h = self._new(NT, ls.si1.dim_out) if t > 0 else None
             if use_t:
                 src_t, w_row_t = g.by_source(lib, st)
-                if L.t_dead:
+                if L.t_dead and not use_m:
                     g_h.zero_()
-                if sh_T is None:
+                if sh_T is None and not use_m:
                     sh_T = self._new(E, nsh)
                     _lib.check(lib.snet_gather_rows(_ptr(sh), _ptr(g.eperm), _ptr(sh_T), E, nsh, st), 'snet_gather_rows')
 
@@ -1000,6 +1022,12 @@ class HipForceEngine:
                 if b <= a:
                     return
                 cp, go = C.c_void_p(g.col_ptr.data_ptr() + 4 * a), C.c_void_p(g_h.data_ptr() + 4 * a * ls.si1.dim_out)
+                if use_m:
+                    with _Span(self, f'conv_bwd_merged[{ls.conv.tag}]'):
+                        _lib.check(lib.snet_lastlayer_conv_bwd(L.mplan, _ptr(h), _ptr(g_m), _ptr(sh), _ptr(dsh), _ptr(g.edge_vec), _ptr(h2),
+                                                               _ptr(h2d), _ptr(g.col_ptr), _ptr(src_t), _ptr(w_row_t), _ptr(g.eperm), a, b,
+                                                               L.scale, _ptr(g_h), _ptr(g_vec), st), 'snet_lastlayer_conv_bwd')
+                    return
                 if use_t:
                     with _Span(self, f'conv_bwd_node[transposed {ls.conv.tag}]'):
                         _lib.check(lib.snet_conv_fwd_fused(L.tplan, _ptr(g_m), _ptr(sh_T), _ptr(h2), _ptr(w_row_t), cp, _ptr(src_t),
@@ -1019,7 +1047,7 @@ class HipForceEngine:
                 h2d = c.h2d_of.pop(t, None)
 
                 def bwd_tiles(tp_, tn_, nt_):
-                    if nt_ <= 0:
+                    if nt_ <= 0 or use_m:   # (merged: gh_rows writes g_vec too)
                         return
                     with _Span(self, f'conv_bwd_fused[{ls.conv.tag}]'):
                         if tangent:

@@ -31,7 +31,7 @@ from typing import Dict
 
 import numpy as np
 
-from .model_spec import (ACT_CST, ACT_ID, LinearSpec, build_model_spec, folded_readout, layer0_moments_eligible, linear_modal_bias,
+from .model_spec import (ACT_CST, ACT_ID, LinearSpec, build_model_spec, folded_readout, lastlayer_merged_eligible, layer0_moments_eligible, linear_modal_bias,
                          linear_weight_matrices, species_only_tables)
 
 MAGIC = b'SNETMDL4'
@@ -160,7 +160,9 @@ def write_model_file(path: str, config: dict, state_dict: Dict[str, np.ndarray],
             'model_type': str(config.get('model_type', 'E3_equivariant_model')),
             'version': str(config.get('version', '')), 'dtype': 'single',
             # model_spec.layer0_moments_eligible (paths, offsets, coupling terms) decided HERE: the sequencer sees dimensions only
-            'layer0_moments': str(int(layer0_moments_eligible(sp.layers[0].conv, sp.layers[0].mlp_dims)))}
+            'layer0_moments': str(int(layer0_moments_eligible(sp.layers[0].conv, sp.layers[0].mlp_dims))),
+            # ... and model_spec.lastlayer_merged_eligible for the last layer's one-launch reverse pass (snet_lastlayer_conv_bwd)
+            'last_layer_merged': str(int(len(sp.layers) > 1 and lastlayer_merged_eligible(sp.layers[-1].conv, sp.layers[-1].mlp_dims)))}
     text = ''.join(f'{k}={v}\n' for k, v in meta.items()).encode()
     out.append(_i(len(text)))
     out.append(text)

@@ -331,6 +331,47 @@ def transposed_scalar_conv(conv: ConvSpec):
     return spec, kappa
 
 
+LASTLAYER_TILES = ((1, 1), (1, 1, 1), (8, 4, 2), (8, 4, 2, 2))   # 16-channel tiles per l the kernels of csrc/snet_lastlayer.hip exist for
+LASTLAYER_LDS_BUDGET = 80 * 1024                                 # bytes per workgroup: two of them share a compute unit's 160 KiB
+
+
+def lastlayer_merged_eligible(conv: ConvSpec, mlp_dims) -> bool:
+    """May the reverse pass of a layer of this shape run as ONE source-grouped launch (csrc/snet_lastlayer.hip) in place of the
+    tangent-mode reverse kernel plus the transposed scalar convolution?  Needs the transposed product, one path (l, l -> 0) per
+    l = 0 .. lmax in l order with the diagonal coupling 1 / sqrt(2 l + 1), source blocks in l order (blocks no path reads may sit
+    between them), weight columns and outputs packed in path order, radial dims [nb, 64, 64, wn], multiplicities a compiled kernel
+    exists for, and the W2 image + the wave-private rows inside the LDS budget: what snet_lastlayer_plan_create cannot see from the
+    dimensions and the column factors, the caller checks here.  (t > 0, fused kernels in both directions, terms = 4 and E > 0 are the
+    hosts' part.)"""
+    from .codegen import _path_terms
+    tr = transposed_scalar_conv(conv)
+    if tr is None or len(mlp_dims) != 4 or tuple(mlp_dims[1:3]) != (64, 64) or mlp_dims[3] != conv.weight_numel:
+        return False
+    lmax = len(conv.paths) - 1
+    if not 0 <= lmax <= 3 or conv.irreps_sh.dim != (lmax + 1) ** 2:
+        return False
+    x_offs, col, prev_x, live = conv.irreps_x.offsets(), 0, -1, 0
+    for l, (p, q, kappa) in enumerate(zip(conv.paths, tr[0].paths, tr[1])):
+        mul, lx, _ = conv.irreps_x[p.i_x]
+        if (p.l1, p.l2, p.l3, lx) != (l, l, 0, l) or p.mul != mul or mul % 16 or p.sh_off != l * l:
+            return False
+        if p.w_off != col or p.out_off + p.out_ch != col or p.x_off != x_offs[p.i_x] or x_offs[p.i_x] <= prev_x:
+            return False
+        # the transposed path (0, l -> l) couples Y_m to component m with factor 1; the forward path carries kappa = 1 / sqrt(2 l + 1)
+        terms = sorted(_path_terms(q))
+        if [(a, b, c) for a, b, c, _ in terms] != [(0, m, m) for m in range(2 * l + 1)] or any(abs(v - 1.0) > 1e-12 for *_, v in terms):
+            return False
+        if abs(kappa - 1.0 / math.sqrt(2 * l + 1)) > 1e-9:
+            return False
+        prev_x, col, live = x_offs[p.i_x], col + mul, live + (2 * l + 1) * mul
+    if col != conv.weight_numel or col != conv.irreps_out.dim or col > 512:
+        return False
+    if tuple(p.mul // 16 for p in conv.paths) not in LASTLAYER_TILES:
+        return False
+    lds = 64 * col * 4 + 4 * 16 * conv.irreps_sh.dim * 4 + 4 * live * 4   # W2 as two fp16 terms; Y tiles and source rows of four waves
+    return lds <= LASTLAYER_LDS_BUDGET
+
+
 def make_conv(irreps_x: Irreps, irreps_sh: Irreps, irreps_target: Irreps, sort_by_out: bool) -> ConvSpec:
     """Instruction generation of sevenn/nn/convolution.py:61-82.  Weight columns
     follow the (possibly re-sorted) instruction order, `mul_x` per instruction;

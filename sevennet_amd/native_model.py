@@ -27,11 +27,14 @@ class _DevRows:
 
 
 class NativeModel:
-    def __init__(self, model, state_dict: Optional[Dict[str, np.ndarray]] = None, device='cuda:0', modal=None, layer0_moments: Optional[bool] = None):
+    def __init__(self, model, state_dict: Optional[Dict[str, np.ndarray]] = None, device='cuda:0', modal=None, layer0_moments: Optional[bool] = None,
+                 last_layer_merged: Optional[bool] = None):
         """model: path of a `.snet` file, or a reference config dict (then `state_dict` is required and
         the file is written to a temporary location first).
         layer0_moments: HipForceEngine's switch (snet_model_set_layer0_moments); None = the sequencer's default (on, unless
-        SNET_LAYER0_MOMENTS=0 is in the environment)."""
+        SNET_LAYER0_MOMENTS=0 is in the environment).
+        last_layer_merged: likewise for the last layer's one-launch reverse pass (snet_model_set_last_layer_merged,
+        SNET_LAST_LAYER_MERGED=0)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError('NativeModel needs a ROCm GPU (no CPU fallback exists)')
@@ -40,6 +43,9 @@ class NativeModel:
         self._load(model, state_dict, modal)
         if layer0_moments is not None:
             _lib.check(self.lib.snet_model_set_layer0_moments(self.handle, int(bool(layer0_moments))), 'snet_model_set_layer0_moments')
+        if last_layer_merged is not None:
+            _lib.check(self.lib.snet_model_set_last_layer_merged(self.handle, int(bool(last_layer_merged))),
+                       'snet_model_set_last_layer_merged')
         cut, ns, nl = C.c_float(), C.c_int32(), C.c_int32()
         comm = (C.c_int32 * 64)()
         _lib.check(self.lib.snet_model_info(self.handle, C.byref(cut), C.byref(ns), C.byref(nl), comm, 64),

@@ -41,6 +41,24 @@ def mini_sevennet_0_config(num_species: int = 2) -> dict:
     return cfg
 
 
+def lastlayer_test_config(irreps: str, lmax: int, parity: bool = False) -> dict:
+    """Two-layer stand-in whose LAST layer has the source irreps `irreps` and 16 scalar outputs per path: the smallest shapes of
+    the one-launch reverse pass (csrc/snet_lastlayer.hip), one 16-channel tile per l."""
+    cfg = sevennet_0_config(1)
+    cfg.update(channel=16, lmax=lmax, is_parity=parity, num_convolution_layer=2, irreps_manual=['16x0e', irreps, '16x0e'],
+               conv_denominator=20.0)
+    return cfg
+
+
+def lastlayer_test_configs() -> Dict[str, dict]:
+    """Shapes that only tests/test_lastlayer_gpu.py runs; built with the library (sevennet_amd.build) but not part of aot_configs()."""
+    return {
+        'last16_l1': lastlayer_test_config('16x0e+16x1e', 1),
+        'last16_l2': lastlayer_test_config('16x0e+16x1e+16x2e', 2),
+        'last16_o3_dead': lastlayer_test_config('16x0e+16x1o+16x1e', 1, True),   # the 1e block feeds no path: a dead range of g_h
+    }
+
+
 def aot_configs() -> Dict[str, dict]:
     return {
         'ts_example': TS_EXAMPLE_CONFIG,
