@@ -585,6 +585,51 @@ int snet_neb_forces(const double *pos, const float *forces, const double *forces
                     const double *cells, const double *inv_cells, const int32_t *pbc, const int32_t *fixed, const double *k,
                     int32_t climb, int32_t *active, int32_t *status, double *f_neb, int32_t *imax, void *stream);
 
+/* ---- batched finite-difference Hessians (harmonic analysis) --------------------------------------
+ * Central differences of forces, as ASE's Vibrations with direction='central'.  For system b let idx_b be the m_b atoms that are
+ * displaced, delta the displacement in A, and F(a,i,q) the summed forces (the engine's fp32 forces widened, plus forces_extra in
+ * fp64) on the atoms idx_b when coordinate i of atom a is moved by q delta.  With the row r = 3 (position of a in idx_b) + i:
+ *   nfree = 2:  D[r,:] = (F(a,i,-1) - F(a,i,+1)) / (2 delta)
+ *   nfree = 4:  D[r,:] = (((8 F(a,i,-1) - F(a,i,-2)) - 8 F(a,i,+1)) + F(a,i,+2)) / (12 delta)
+ *   H  = (D + D^T) 0.5                              eV/A^2
+ *   asymmetry = max |D - D^T|                       the noise floor of fp32 forces at this delta
+ *   Hm[r,c] = H[r,c] (w_r w_c),  w = 1 / sqrt(mass in amu) of the row's / column's atom       (bitwise symmetric, like H)
+ * and on the host (sevennet_amd/vib.py): lambda = the eigenvalues of Hm, ascending, in eV/(A^2 amu);
+ *   h nu = hbar sqrt(ACC |lambda|) sign(lambda) with hbar = 0.6582119569 eV fs and ACC = 9.648533212e-3, so an imaginary mode is
+ *   reported as a negative number; frequencies = h nu 8065.543937 cm^-1/eV; zpe = (1/2) sum of the positive h nu.
+ * Every expression is evaluated in fp64 in the order written, no product contracted with a sum, so the results equal the numpy
+ * restatement (tests/vib_ref.py) bit for bit.  One 256-thread workgroup per unit of work, no atomics: two runs give identical bits.
+ *
+ * snet_vib_displace writes the displaced copies.  pos0 (fp64 [n0,3]) holds the base positions, system b being rows
+ * [seg_ptr0[b], seg_ptr0[b+1]) (int32 [n_sys+1]).  Copy j is described by desc[4 j ..] = (system, atom within the system, axis,
+ * multiplier q in -2 .. 2) (int32 [n_copies,4]) and owns rows [copy_ptr[j], copy_ptr[j+1]) (int32 [n_copies+1]) of pos_out (fp64
+ * [n_out,3]): they receive the system's rows with q delta added to the one component -- the product is rounded, then added; q = 0
+ * is the undisplaced copy, bit for bit.  A descriptor that does not fit -- a system, atom, axis or multiplier out of range, base or
+ * output rows outside their arrays, a copy span that differs from the system's atom count -- sets status[j] = 1 (int32
+ * [n_copies], otherwise left as it is) and leaves its rows unwritten; it is refused before anything is read or written.
+ *
+ * snet_vib_rows turns the forces on the copies of ONE call into rows of D.  forces (fp32 [n_atoms,3]) and forces_extra (fp64
+ * [n_atoms,3] or NULL) are those of the n_copies copies of the call, copy j being rows [seg_ptr[j], seg_ptr[j+1]).  Row group g
+ * is group[3 g ..] = (first copy j0, system b, row r) (int32 [n_groups,3]): its nfree copies j0 .. j0 + nfree - 1 are adjacent, in
+ * the order q = -1, +1 or q = -2, -1, +1, +2.  The selected atoms of system b are sel[sel_ptr[b] .. sel_ptr[b+1]) (int32, indices
+ * within the system; sel_ptr int32 [n_sys+1], n_sel entries in all).  Row r of the [3 m_b, 3 m_b] block that starts at D[d_off[b]]
+ * (d_off int64 [n_sys], D fp64 [d_size]) is WRITTEN, not accumulated: each row is written by one workgroup of one call, so the
+ * result does not depend on how the rows are spread over calls.  A force that is not finite sets status[b] = 2 (int32 [n_sys]); a
+ * group that does not fit (copies outside the call, copies of unequal size, a row or block outside D, a selected atom outside the
+ * system) sets status[b] = 3 and writes nothing outside the arrays.
+ *
+ * snet_vib_finish, once after the last call, one workgroup per system: reads D and writes H, Hm (fp64 [d_size], the same blocks)
+ * and asymmetry[b]; w (fp64 [n_sel]) holds 1 / sqrt(mass) of the selected atoms.  For a system with status[b] != 0 the three are
+ * NaN.                                                                                                                        */
+int snet_vib_displace(const double *pos0, int64_t n0, const int32_t *seg_ptr0, int32_t n_sys, const int32_t *desc,
+                      const int32_t *copy_ptr, int32_t n_copies, double delta, double *pos_out, int64_t n_out, int32_t *status,
+                      void *stream);
+int snet_vib_rows(const float *forces, const double *forces_extra, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_copies,
+                  const int32_t *group, int32_t n_groups, int32_t nfree, double delta, const int32_t *sel, const int32_t *sel_ptr,
+                  int64_t n_sel, const int64_t *d_off, int32_t n_sys, double *D, int64_t d_size, int32_t *status, void *stream);
+int snet_vib_finish(const double *D, const int64_t *d_off, const int32_t *sel_ptr, int64_t n_sel, const double *w, int32_t n_sys,
+                    int64_t d_size, int32_t *status, double *H, double *Hm, double *asymmetry, void *stream);
+
 /* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
  * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
  * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of

@@ -223,6 +223,7 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         self.relax_info: Optional[Dict[str, int]] = None   # counters of the last relax_many call
         self.md_info: Optional[Dict[str, int]] = None      # counters of the last md_many call
         self.neb_info: Optional[Dict[str, int]] = None     # counters of the last neb_many call
+        self.vib_info: Optional[Dict[str, int]] = None     # counters of the last vibrations_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -324,6 +325,27 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         results, self.neb_info = neb_batch(self.model, self._types_list(numbers_list), list(images_list), cells, pbcs,
                                            cutoff=self.cutoff, fmax=fmax, steps=steps,
                                            want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def vibrations_many(self, numbers_list, positions_list, masses_list, cells, pbcs, **kw) -> List[Dict[str, Any]]:
+        """Harmonic analysis of B structures at once (sevennet_amd.vib.vibrations_batch): the finite-difference Hessian of each
+        by central differences of forces, as ASE's Vibrations does it, with the displaced copies written, evaluated in batches
+        and reduced on the GPU.  masses_list in amu (the caller's: this package has no table of atomic masses).  kw: delta
+        (the displacement in A, default 0.01), nfree (2 or 4 displacements per coordinate), indices (per system None, a bool
+        mask or a list of the atoms that are displaced; the others are held fixed), max_atoms_per_call (a cap on the atoms of
+        one batched evaluation) and extra / make_extra (as vibrations_batch).  One dict per system, in the given order: the
+        keys of `compute` for the undisplaced structure (is it a stationary point?; its per-atom energies are
+        `atomic_energies` here) plus `indices`, `hessian` [3m,3m] (eV/A^2), `asymmetry`, `eigenvalues` (of the mass-weighted Hessian, ascending), `modes` [3m,m,3], `energies` (h nu, eV) and `frequencies`
+        (cm^-1) -- both signed: an imaginary mode is a negative number, so a minimum has none below zero and a first-order
+        saddle, the top of a climbing-image band of `neb_many`, exactly one -- `zpe` (eV) and `status` ('ok' or 'failed').
+        vib.harmonic_prefactor turns the `energies` of a minimum and of a saddle into the prefactor of the hop.  The call's
+        counters are kept as `self.vib_info`."""
+        from .vib import vibrations_batch
+        if not len(numbers_list) == len(positions_list) == len(masses_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '
+                             f'{len(masses_list)} mass arrays')
+        results, self.vib_info = vibrations_batch(self.model, self._types_list(numbers_list), list(positions_list), list(masses_list),
+                                                  cells, pbcs, cutoff=self.cutoff, want_atomic_virial=self.compute_atomic_virial, **kw)
         return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:

@@ -351,6 +351,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         self.relax_info = None   # counters of the last relax_many call
         self.md_info = None      # counters of the last md_many call
         self.neb_info = None     # counters of the last neb_many call
+        self.vib_info = None     # counters of the last vibrations_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -443,6 +444,29 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         for r in results:
             r['images'] = [self._sum(a, next(it)) for a in r['images']]
         return results
+
+    def vibrations_many(self, numbers_list, positions_list, masses_list, cells, pbcs, d3_term: str = 'host', **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.vibrations_many` on the sum of the model's and the D3 forces (sevennet_amd.vib): the Hessians and
+        spectra are those of model + D3, the keys of `compute` for the undisplaced structures are the summed ones.  The
+        counters are kept as `self.vib_info`.  d3_term as in `relax_many`: 'host' prepares the D3 batch of each call's copies
+        on the host, 'device' keeps the term on the device, planned once per layout of the copy slots (vib.plan_copies)."""
+        self._check_d3_term(d3_term)
+        snet, d3 = self.calcs
+        numbers_list, positions_list = list(numbers_list), [np.asarray(p, np.float64) for p in positions_list]
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        B = len(numbers_list)
+        cells_b = np.asarray(cells, np.float64).reshape(-1, 3, 3)
+        pbcs_b = np.broadcast_to(np.asarray(pbcs, bool).reshape(-1, 3), (B, 3))
+
+        def make_extra(slot_system):   # the D3 term over the copy slots: slot s holds a copy of system slot_system[s]
+            return self._d3_term([numbers_list[b] for b in slot_system], [positions_list[b] for b in slot_system],
+                                 cells_b[slot_system], pbcs_b[slot_system], d3_term)
+
+        results = snet.vibrations_many(numbers_list, positions_list, masses_list, cells, pbcs, make_extra=make_extra, **kw)
+        self.vib_info = snet.vib_info
+        at_base = d3.compute_many(numbers_list, positions_list, cells, pbcs)
+        return [self._sum(a, b) for a, b in zip(results, at_base)]
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, d3_term: str = 'host',
                 **kw) -> List[Dict[str, Any]]:
