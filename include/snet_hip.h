@@ -630,6 +630,62 @@ int snet_vib_rows(const float *forces, const double *forces_extra, int64_t n_ato
 int snet_vib_finish(const double *D, const int64_t *d_off, const int32_t *sel_ptr, int64_t n_sel, const double *w, int32_t n_sys,
                     int64_t d_size, int32_t *status, double *H, double *Hm, double *asymmetry, void *stream);
 
+/* ---- batched supercell phonons ---------------------------------------------------------------------
+ * Finite-displacement phonons of fully periodic crystals.  System b is a primitive cell C_b (rows), its m_b atoms and repeats
+ * (n1,n2,n3) >= 1.  The supercell lattice is S = diag(n) C; supercell atom j = c m + beta is home atom beta shifted by
+ * (c1,c2,c3) C with c = (c1 n2 + c2) n3 + c3; the home cell is c = 0, so the home atoms are the first m_b of the N_b = m_b n1 n2 n3.
+ *   Force constants: Phi[(alpha,i),(j,k)], a [3 m_b, 3 N_b] array, row r = 3 alpha + i, column 3 j + k: the central difference of
+ *     the forces on ALL N_b atoms when home atom alpha moves along axis i -- the stencil of snet_vib_rows, in its operation order.
+ *   Acoustic sum rule: asr_defect = max over (alpha,i,k) of |sum_j Phi[(alpha,i),(j,k)]|, taken before any correction; with
+ *     `acoustic` set, Phi[(alpha,i),(alpha,k)] is replaced by -sum_{j != alpha} Phi[(alpha,i),(j,k)].  Both sums run in ascending j.
+ *   Images of the pair (alpha, j): d0 = r_j - r_alpha; f_c = (d0_x Sinv[0][c] + d0_y Sinv[1][c]) + d0_z Sinv[2][c]; n0 = -rint(f);
+ *     the candidates are n = n0 + (x,y,z), x,y,z in {-1,0,1}, with d_c = d0_c + ((n1 S[0][c] + n2 S[1][c]) + n3 S[2][c]) and
+ *     |d| = sqrt((d_x^2 + d_y^2) + d_z^2); a candidate is kept when |d| <= min |d| + symprec, and the kept ones share the weight
+ *     equally.  The 27 candidates hold every nearest image when S is Minkowski-reduced, which the driver checks on the host.
+ *   Dynamical matrix at q_cart (rad/A): R(q)[(alpha,i),(beta,k)] = (w_alpha w_beta) sum_c Phi[(alpha,i),(c m + beta,k)] p(alpha, c m +
+ *     beta), c ascending, with the pair's phase p = (sum over the kept d of exp(i q_cart . d)) / n_kept, summed in ascending (x,y,z),
+ *     q . d = (q_x d_x + q_y d_y) + q_z d_z and w = 1 / sqrt(mass in amu); D(q) = (R + R^H) 0.5; hermiticity = max |R - R^H|.
+ *     The phase is taken with the full vector d, so eigenvectors are in that convention (no extra factor exp(i q . r_beta)).
+ * fp64 throughout, one 256-thread workgroup per unit of work, no atomics, every output element written by one thread and every
+ * sum in the order written: two runs give identical bits.  The numpy restatement is tests/phonon_ref.py.
+ *
+ * Shared descriptors: m_ptr (int32 [n_sys+1]): the home atoms of system b are entries [m_ptr[b], m_ptr[b+1]) of the per-home-atom
+ * arrays; sc_ptr (int32 [n_sys+1]): its supercell atoms are rows [sc_ptr[b], sc_ptr[b+1]) of pos (fp64 [n_atoms,3]); p_off (int64
+ * [n_sys]): its block of Phi starts at phi[p_off[b]] (fp64 [p_size]); i_off (int64 [n_sys]): entry (alpha, j) of its image arrays
+ * is i_off[b] + alpha N_b + j (img_base int32 [i_size,3], img_mask int32 [i_size]).  A descriptor that does not fit -- a range
+ * outside its array, N_b no multiple of m_b, a block outside its buffer -- sets status[b] = 3 (int32 [n_sys]) and nothing of that
+ * unit of work is read or written.
+ *
+ * snet_ph_rows is snet_vib_rows with rows over all atoms of the copy: forces / forces_extra / seg_ptr / group / nfree / delta as
+ * there (group[3 g ..] = (first copy, system, row r in [0, 3 m_b)); every copy of the group must hold N_b atoms).  Row r of Phi is
+ * WRITTEN, not accumulated.  A force that is not finite sets status[b] = 2.
+ * snet_ph_finish, one workgroup per system: writes asr_defect[b] and phi_out (fp64 [p_size], the same blocks, not phi itself): phi
+ * with the self terms corrected if `acoustic`, copied otherwise.  For a system with status[b] != 0 both are NaN throughout.
+ * snet_ph_images, one workgroup per home atom (home_sys int32 [n_home]: the system of each): reads pos, S and S_inv (fp64
+ * [n_sys,9] each, row-major; S_inv is the caller's, so that device and restatement wrap with the same bits) and writes img_base =
+ * n0 and img_mask, where bit 9 (x+1) + 3 (y+1) + (z+1) marks a kept candidate.  A pair whose f is not finite keeps no image and
+ * sets status[b] = 3.
+ * snet_ph_dynmat: q-point g of the launch (q_cart fp64 [n_q,3]) belongs to system q_sys[g] (int32 [n_q]) and is number
+ * g - q_ptr[b] of its q_ptr[b+1] - q_ptr[b] points (q_ptr int32 [n_sys+1]); its [3 m_b, 3 m_b] complex blocks of R and D (fp64
+ * [d_size,2]: real, imaginary) start at complex element d_off[b] + (g - q_ptr[b]) 9 m_b^2 (d_off int64 [n_sys]), its hermiticity is
+ * hermiticity[g] (fp64 [n_q]).  w (fp64 [n_home]) holds 1 / sqrt(mass) of the home atoms, max_m the largest m_b (<= 65535).  Two
+ * launches: one workgroup per (q, alpha) computes each pair's phase once, stages the phases in LDS (1024 at a time) and reuses
+ * them for the pair's nine entries; then one workgroup per q writes D and the hermiticity.  D equals D^H bit for bit.  Values
+ * that are not finite (the Phi of a failed system) pass through: R and D are NaN there and so is the hermiticity.              */
+int snet_ph_rows(const float *forces, const double *forces_extra, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_copies,
+                 const int32_t *group, int32_t n_groups, int32_t nfree, double delta, const int32_t *m_ptr, const int32_t *sc_ptr,
+                 const int64_t *p_off, int32_t n_sys, double *phi, int64_t p_size, int32_t *status, void *stream);
+int snet_ph_finish(const double *phi, const int64_t *p_off, const int32_t *m_ptr, const int32_t *sc_ptr, int32_t n_sys, int64_t p_size,
+                   int32_t acoustic, int32_t *status, double *phi_out, double *asr_defect, void *stream);
+int snet_ph_images(const double *pos, int64_t n_atoms, const int32_t *sc_ptr, const int32_t *m_ptr, const int32_t *home_sys,
+                   int32_t n_home, const double *S, const double *S_inv, const int64_t *i_off, int32_t n_sys, double symprec,
+                   int32_t *img_base, int32_t *img_mask, int64_t i_size, int32_t *status, void *stream);
+int snet_ph_dynmat(const double *phi, const int64_t *p_off, int64_t p_size, const double *pos, int64_t n_atoms, const int32_t *sc_ptr,
+                   const int32_t *m_ptr, const double *w, int32_t n_home, const double *S, const int32_t *img_base,
+                   const int32_t *img_mask, const int64_t *i_off, int64_t i_size, const double *q_cart, const int32_t *q_sys,
+                   const int32_t *q_ptr, int32_t n_q, const int64_t *d_off, int32_t n_sys, int32_t max_m, int32_t *status, double *R,
+                   double *D, int64_t d_size, double *hermiticity, void *stream);
+
 /* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
  * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
  * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of

@@ -224,6 +224,7 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         self.md_info: Optional[Dict[str, int]] = None      # counters of the last md_many call
         self.neb_info: Optional[Dict[str, int]] = None     # counters of the last neb_many call
         self.vib_info: Optional[Dict[str, int]] = None     # counters of the last vibrations_many call
+        self.phonon_info: Optional[Dict[str, int]] = None  # counters of the last phonons_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -346,6 +347,35 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
                              f'{len(masses_list)} mass arrays')
         results, self.vib_info = vibrations_batch(self.model, self._types_list(numbers_list), list(positions_list), list(masses_list),
                                                   cells, pbcs, cutoff=self.cutoff, want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def phonons_many(self, numbers_list, positions_list, masses_list, cells, pbcs, supercells, *, qpoints=None, mesh=None,
+                     temperatures=None, delta: float = 0.01, nfree: int = 2, acoustic: bool = True, symprec: float = 1e-5,
+                     want_modes: bool = False, dos_bins=200, max_atoms_per_call: int = 32768, **kw) -> List[Dict[str, Any]]:
+        """Supercell phonons of B crystals at once (sevennet_amd.phonon.phonons_batch).  numbers_list / positions_list / masses_list
+        (amu) / cells / pbcs describe the PRIMITIVE cells (fully periodic), supercells the repeats (n1,n2,n3): one triple or one per
+        system.  Only the home-cell atoms are displaced (nfree 3 m supercells per system, packed into batched evaluations of at
+        most max_atoms_per_call atoms); the force constants against the whole supercell, the acoustic sum rule (acoustic), the
+        nearest-image rule (symprec, A: equally near images share the weight) and the dynamical matrices D(q) are computed on the
+        GPU.  qpoints: fractional q-points ([n_q,3], or one array per system; phonon.band_path makes a path); mesh: a
+        Gamma-centred mesh for `dos` and, with temperatures (K), `thermo`; at least one of the two.  Further kw: e_min,
+        max_q_per_call, extra / make_extra (as phonons_batch).  One dict per system, in the given order: the keys of `compute` for
+        the undisplaced supercell (per-atom energies as `atomic_energies`) plus `supercell`, `supercell_positions`,
+        `supercell_cell`, `force_constants` [m,N,3,3], `asr_defect`, `qpoints`, `eigenvalues`, `energies` (h nu in eV) and
+        `frequencies` (cm^-1) [n_q,3m] -- both signed: an imaginary mode is a negative number --, `hermiticity` [n_q], `modes`
+        [n_q,3m,m,3] (want_modes; the phase of D(q) is taken with the full vector between the atoms, and the modes are in that
+        convention), with mesh `mesh`, `dos_energies`, `dos`, `thermo`, and `status` ('ok' or 'failed').  The call's counters
+        are kept as `self.phonon_info`."""
+        from .phonon import phonons_batch
+        if not len(numbers_list) == len(positions_list) == len(masses_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '
+                             f'{len(masses_list)} mass arrays')
+        results, self.phonon_info = phonons_batch(self.model, self._types_list(numbers_list), list(positions_list), list(masses_list),
+                                                  cells, pbcs, supercells, cutoff=self.cutoff, qpoints=qpoints, mesh=mesh,
+                                                  temperatures=temperatures, delta=delta, nfree=nfree, acoustic=acoustic,
+                                                  symprec=symprec, want_modes=want_modes, dos_bins=dos_bins,
+                                                  max_atoms_per_call=max_atoms_per_call,
+                                                  want_atomic_virial=self.compute_atomic_virial, **kw)
         return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:

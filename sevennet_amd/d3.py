@@ -352,6 +352,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         self.md_info = None      # counters of the last md_many call
         self.neb_info = None     # counters of the last neb_many call
         self.vib_info = None     # counters of the last vibrations_many call
+        self.phonon_info = None  # counters of the last phonons_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -466,6 +467,35 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         results = snet.vibrations_many(numbers_list, positions_list, masses_list, cells, pbcs, make_extra=make_extra, **kw)
         self.vib_info = snet.vib_info
         at_base = d3.compute_many(numbers_list, positions_list, cells, pbcs)
+        return [self._sum(a, b) for a, b in zip(results, at_base)]
+
+    def phonons_many(self, numbers_list, positions_list, masses_list, cells, pbcs, supercells, d3_term: str = 'host',
+                     **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.phonons_many` on the sum of the model's and the D3 forces (sevennet_amd.phonon): the force constants
+        and everything that follows from them are those of model + D3, the keys of `compute` for the undisplaced supercells are
+        the summed ones.  The counters are kept as `self.phonon_info`.  d3_term as in `vibrations_many`: the term is built over
+        the copy slots of the supercells (make_extra)."""
+        from .phonon import build_supercell
+        self._check_d3_term(d3_term)
+        snet, d3 = self.calcs
+        numbers_list, positions_list = list(numbers_list), [np.asarray(p, np.float64) for p in positions_list]
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        built = {}   # the supercells as the driver builds them, made when it asks for the term: its validation has passed by then
+
+        def make_extra(slot_system):   # the D3 term over the copy slots: slot s holds a copy of the supercell of system slot_system[s]
+            B = len(numbers_list)
+            cells_b = np.asarray(cells, np.float64).reshape(-1, 3, 3)
+            reps = np.asarray(supercells, np.int64)
+            reps = np.tile(reps, (B, 1)) if reps.ndim == 1 else reps
+            sc = [build_supercell(numbers_list[b], positions_list[b], cells_b[b], reps[b]) for b in range(B)]
+            built.update(numbers=[s[0] for s in sc], positions=[s[1] for s in sc], cells=np.stack([s[2] for s in sc]))
+            return self._d3_term([built['numbers'][b] for b in slot_system], [built['positions'][b] for b in slot_system],
+                                 built['cells'][slot_system], np.ones((len(slot_system), 3), bool), d3_term)
+
+        results = snet.phonons_many(numbers_list, positions_list, masses_list, cells, pbcs, supercells, make_extra=make_extra, **kw)
+        self.phonon_info = snet.phonon_info
+        at_base = d3.compute_many(built['numbers'], built['positions'], built['cells'], np.ones((len(numbers_list), 3), bool))
         return [self._sum(a, b) for a, b in zip(results, at_base)]
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, d3_term: str = 'host',
