@@ -100,6 +100,31 @@ typedef struct snet_gemm_desc {
 #define SNET_MAX_GEMM_GROUP 8
 int snet_gemm_grouped(const snet_gemm_desc *descs_host, int32_t n_desc, const float *A, float *C, int64_t n_nodes,
                       int64_t a_node_stride, int64_t c_node_stride, const int32_t *row_idx, void *stream);
+/* Two-source grouped GEMM (split-packed weights only): every problem writes ONE output block from one or two operand pairs,
+ *   C[node, c_off + m*N + :] = A0[node, a_off0 + m*K0 + :] B0  (+ A1[node, a_off1 + m*K1 + :] B1)  (+ table[types[node], same columns])
+ * in one launch: the k loop runs through source 0's k steps and then source 1's, each source into its own accumulators, which are
+ * added once at the single (non-accumulating) store.  It replaces a writing launch followed by an accumulating one over the same
+ * rows (y = SI2(m) + sc(x), g_x = sc^T(g_y) + SI1^T(g_h)) and returns that pair's bits: the accumulating epilogue added the same
+ * two numbers.  Each source has its own base pointer, node stride, offset and K; all
+ * problems of a launch share C, its node stride, the row list and n_nodes.  `table` (with `types`, both device, or both NULL):
+ * fp32 [n_types, c_node_stride], addressed like C; its row is added in the epilogue (layer 0's species-only self-connection).
+ * With one source and no table the result is bit-identical to snet_gemm_grouped.  A source whose weights are fp32 (`B`) is
+ * refused, alone or mixed with packed ones; n_nodes <= 0 returns 0.                                                          */
+#define SNET_GEMM_MAX_SRC 2
+typedef struct snet_gemm_src {
+  const float *A;       /* device rows of this source */
+  const float *B;       /* fp32 weights: not served here (must be NULL) */
+  const void *B_split;  /* device copy of a snet_gemm_split_pack buffer of [K,N] */
+  int64_t a_node_stride, a_off;
+  int32_t K, reserved;
+} snet_gemm_src;
+typedef struct snet_gemm_multi_desc {
+  snet_gemm_src src[SNET_GEMM_MAX_SRC];
+  int64_t c_off;
+  int32_t n_src, d, N, reserved;
+} snet_gemm_multi_desc;
+int snet_gemm_multi(const snet_gemm_multi_desc *descs_host, int32_t n_desc, float *C, int64_t n_nodes, int64_t c_node_stride,
+                    const int32_t *row_idx, const float *table, const int32_t *types, void *stream);
 /* weights [K,N] (HOST, fp32, normalisation folded) -> matrix-core B fragments, each value written as
  * a sum of three bf16 terms (HOST buffer of snet_gemm_split_size bytes; upload it and pass the device
  * copy as snet_gemm_desc.B_split).  All problems of one grouped launch must use the same kind. */

@@ -30,6 +30,16 @@ class GemmDesc(C.Structure):
                 ('N', C.c_int32), ('accumulate', C.c_int32)]
 
 
+class GemmSrc(C.Structure):
+    _fields_ = [('A', C.c_void_p), ('B', C.c_void_p), ('B_split', C.c_void_p), ('a_node_stride', C.c_int64), ('a_off', C.c_int64),
+                ('K', C.c_int32), ('reserved', C.c_int32)]
+
+
+class GemmMultiDesc(C.Structure):
+    _fields_ = [('src', GemmSrc * 2), ('c_off', C.c_int64), ('n_src', C.c_int32), ('d', C.c_int32), ('N', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 class GateSeg(C.Structure):
     _fields_ = [('kind', C.c_int32), ('in_off', C.c_int32), ('out_off', C.c_int32), ('mul', C.c_int32),
                 ('l', C.c_int32), ('gate_off', C.c_int32), ('act', C.c_int32), ('cst', C.c_float)]
@@ -57,6 +67,8 @@ SIGNATURES = {
                             C.c_int64, C.c_int64, C.c_int64, c_i32p, C.c_int32, c_stream]),
     'snet_gemm_grouped': (C.c_int, [C.POINTER(GemmDesc), C.c_int32, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_int64,
                                     c_i32p, c_stream]),
+    'snet_gemm_multi': (C.c_int, [C.POINTER(GemmMultiDesc), C.c_int32, c_f32p, C.c_int64, C.c_int64, c_i32p, c_f32p, c_i32p,
+                                  c_stream]),
     'snet_gemm_split_size': (C.c_int64, [C.c_int32, C.c_int32]),
     'snet_gemm_split_pack': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     'snet_act_fwd': (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_float, c_stream]),

@@ -448,6 +448,244 @@ __global__ __launch_bounds__(256, MT == 1 ? SNET_GEMM_OCC : 2) void gemm_split_g
                            row_idx, P.accumulate);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two-source variant of the split-precision kernel: C = A0 B0 (+ A1 B1) (+ table[types[node]]), written ONCE.  The k loop of
+// gemm_split_body runs over source 0's k steps and then over source 1's, the double-buffered B slab keeps going across the
+// boundary, and the plain epilogue stores.  It serves y = SI2(m) + sc(x) and g_x = sc^T(g_y) + SI1^T(g_h), which used to be a
+// writing launch followed by an accumulating one over the same rows (one write + one read of the rows and one launch more).
+//
+// Each source has its OWN accumulators, added once at the store: acc0 + acc1 is exactly what the accumulating epilogue computed
+// (the stored product of one launch plus the accumulators of the other), so the result is bit-identical to the pair of launches.
+// One accumulator set running through both sources -- one rounding fewer on paper -- was measured and is NOT taken: every matrix
+// instruction of source 1 then rounds at the magnitude of the sum, and against fp64 the error was 1.35 .. 1.8 times the pair's at
+// K = 224 + 128 (1.0 .. 1.14 at K = 20 + 8), outside the project's 1.5 bar (same finding as "accumulators started from C" below
+// gemm_split_body).  Two sets of a 128-column tile do not fit 128 VGPRs, so a two-source problem uses 64-column tiles (NT = 2,
+// the register budget of a one-source NT = 4 tile); the column blocks of a row block are neighbouring workgroups (by is the
+// fast index), so the A rows they share are read from memory once and from cache after that.
+struct MultiSrc {
+  const float *A;
+  const snet::u32x4 *Bp;
+  int64_t a_node_stride, a_off;
+  int K, nq;
+};
+struct MultiProb {
+  MultiSrc s[2];   // a one-source problem carries a copy of source 0 with nq = 0 in s[1]
+  int64_t c_off;
+  int d, N;
+};
+struct MultiArgs {
+  int n;
+  int first_block[SNET_MAX_GEMM_GROUP + 1];
+  int nby[SNET_MAX_GEMM_GROUP];   // column blocks per problem
+  MultiProb p[SNET_MAX_GEMM_GROUP];
+};
+
+// epilogue with the per-node constant row: C = acc + table[types[node]] (one rounding), the table addressed like C.  Loads of a
+// chunk of rows are issued before its first store, as in the accumulating epilogue of gemm_split_store.
+template <int NT>
+__device__ __forceinline__ void gemm_multi_store_table(const snet::f32x16 (&acc)[1][NT], const RowMap &rows, int64_t row0, int half,
+    int li, int tile0, float *__restrict__ C, int64_t n_rows, int N, int64_t c_node_stride, int64_t c_off,
+    const int32_t *__restrict__ row_idx, const float *__restrict__ table, const int32_t *__restrict__ types) {
+#pragma unroll
+  for (int j0 = 0; j0 < 16; j0 += 4) {
+    float *crow[4];
+    float add[4][NT];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int j = j0 + jj, off = (j & 3) + 8 * (j >> 2) + 4 * half;
+      crow[jj] = nullptr;
+      const float *trow = nullptr;
+      if (row0 + off < n_rows) {
+        int64_t n;
+        int m;
+        rows.at(off, n, m);
+        const int64_t node = row_idx ? (int64_t)row_idx[n] : n;
+        crow[jj] = C + node * c_node_stride + c_off + (int64_t)m * N;
+        trow = table + (int64_t)types[node] * c_node_stride + c_off + (int64_t)m * N;
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int col = 32 * (tile0 + t) + li;
+        add[jj][t] = (trow != nullptr && col < N) ? trow[col] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int col = 32 * (tile0 + t) + li;
+        if (crow[jj] != nullptr && col < N) crow[jj][col] = acc[0][t][j0 + jj] + add[jj][t];
+      }
+  }
+}
+
+template <int NT, int NS>   // NS = number of sources = accumulator sets
+__device__ __forceinline__ void gemm_multi_body(snet::u32x4 *Bs, int bx, int by, const MultiProb &P, float *__restrict__ C,
+    int64_t n_rows, int64_t c_node_stride, const int32_t *__restrict__ row_idx, const float *__restrict__ table,
+    const int32_t *__restrict__ types) {
+  using namespace snet;
+  constexpr int SLAB = NT * 192;  // u32x4 per k step
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int half = lane >> 5, li = lane & 31;
+  const int64_t row0 = ((int64_t)bx * 4 + wave) * 32;
+  const int N = P.N, n_tiles = (N + 31) >> 5, tile0 = by * NT;
+  const int nq0 = P.s[0].nq, nq_all = nq0 + (NS > 1 ? P.s[1].nq : 0);
+  const RowMap rows(row0, P.d);
+  const bool a_ok = row0 + li < n_rows;
+
+  // The operand state of the NEXT k step to load: step q of the current source.  One A pointer is live at a time (the kernel sits at
+  // the register limit of 4 waves per SIMD); at the boundary (wave-uniform branch, once per block) the lane's row address is taken
+  // again for source 1: same (node, m), its own base, node stride, offset and K.
+  int q = 0, K = 0, nq = 0;
+  bool a_vec = false;
+  const float *ap = nullptr;                 // the lane's 8 floats of step q
+  const u32x4 *__restrict__ Bp = nullptr;
+  auto enter_source = [&](const MultiSrc &S) {
+    int64_t n = 0;
+    int m = 0;
+    int l_ = li;
+    asm volatile("" : "+v"(l_));   // opaque: the row map is evaluated here, not hoisted out of the k loop and kept (spilled) across it
+    if (a_ok) rows.at(l_, n, m);
+    const int64_t node = row_idx ? (int64_t)row_idx[n] : n;   // (rows past the end: the first row's node, m 0 -- valid memory, never stored)
+    q = 0;
+    K = S.K;
+    nq = S.nq;
+    Bp = S.Bp;
+    ap = S.A + node * S.a_node_stride + S.a_off + (int64_t)m * S.K + 8 * half;
+    a_vec = ((S.K & 3) == 0) && ((S.a_off & 3) == 0) && ((S.a_node_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(S.A) & 15) == 0);
+  };
+  auto next_step = [&]() {
+    ++q;
+    ap += 16;
+    if (NS > 1 && q == nq) enter_source(P.s[1]);   // (only called while a step is left, so this is the end of source 0)
+  };
+  auto load_a = [&](float (&v)[8]) {
+    const int k = 16 * q + 8 * half;
+    if (a_ok && a_vec && k + 7 < K) {
+      const f32x4 lo = *reinterpret_cast<const f32x4 *>(ap);
+      const f32x4 hi = *reinterpret_cast<const f32x4 *>(ap + 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { v[i] = lo[i]; v[4 + i] = hi[i]; }
+    } else {   // a source's last k step may be partial (K = 20): zero-filled
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = (a_ok && k + i < K) ? ap[i] : 0.f;
+    }
+  };
+  constexpr int NST = (SLAB + 255) / 256;
+  // fragment `rem` of column tile tile0 + t, k step q: a 32-bit BYTE offset from the (wave-uniform) packed buffer -- the entry point
+  // refuses buffers of 4 GiB and more -- so that the address is scalar base + one VGPR (64-bit indices, which change with the source,
+  // cost two VGPRs per load in flight: spills at this kernel's register limit)
+  auto b_at = [&](int t, int rem) -> u32x4 {
+    const uint32_t byte_off = (((uint32_t)(tile0 + t) * (uint32_t)nq + (uint32_t)q) * 192u + (uint32_t)rem) * 16u;
+    return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(Bp) + byte_off);
+  };
+  auto load_b = [&](u32x4 (&st)[NST]) {
+    if (tile0 + NT <= n_tiles) {   // all NT column tiles exist (wave-uniform): no per-thread tile test
+#pragma unroll
+      for (int i = 0; i < NST; ++i) {
+        const int idx = tid + 256 * i;
+        const int t = idx / 192, rem = idx - 192 * t;
+        if (SLAB % 256 == 0 || idx < SLAB) st[i] = b_at(t, rem);
+      }
+      return;
+    }
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+      const int idx = tid + 256 * i;
+      const int t = idx / 192, rem = idx - 192 * t;
+      u32x4 z = {0u, 0u, 0u, 0u};
+      if (idx < SLAB && tile0 + t < n_tiles) z = b_at(t, rem);
+      st[i] = z;
+    }
+  };
+  auto store_b = [&](int buf, const u32x4 (&st)[NST]) {
+#pragma unroll
+    for (int i = 0; i < NST; ++i) {
+      const int idx = tid + 256 * i;
+      if (idx < SLAB) Bs[buf * SLAB + idx] = st[i];
+    }
+  };
+
+  f32x16 acc[1][NT];   // source 0's accumulators, and the sum at the store
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[0][t] = zero16();
+  float av[8], an[8];
+  u32x4 st[NST];
+  enter_source(P.s[0]);
+  load_a(av);
+  load_b(st);
+  store_b(0, st);
+  __syncthreads();
+  int buf = 0;
+  // k steps [s0, s1) of the launch into one accumulator set; the prefetch of step s + 1 runs on into the next source
+  auto k_steps = [&](f32x16 (&ac)[NT], int s0, int s1) {
+    for (int s = s0; s < s1; ++s) {
+      const bool more = s + 1 < nq_all;
+      if (more) {
+        next_step();
+        load_a(an);
+        load_b(st);
+      }
+      const Split3 a = split8(av);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        bf16x8 b[3];
+#pragma unroll
+        for (int term = 0; term < 3; ++term) b[term] = as_bf16x8(Bs[buf * SLAB + (t * 3 + term) * 64 + lane]);
+        ac[t] = mfma6(a, b, ac[t]);
+      }
+      if (more) {
+        store_b(buf ^ 1, st);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) av[i] = an[i];
+      }
+      __syncthreads();
+      buf ^= 1;
+    }
+  };
+  k_steps(acc[0], 0, nq0);
+  if constexpr (NS > 1) {
+    f32x16 acc1[NT];   // source 1's accumulators
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc1[t] = zero16();
+    k_steps(acc1, nq0, nq_all);
+    // one rounding per entry: what the accumulating epilogue did with the stored product of the other launch
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[0][t][j] += acc1[t][j];
+  }
+
+  if (table != nullptr)
+    gemm_multi_store_table<NT>(acc, rows, row0, half, li, tile0, C, n_rows, N, c_node_stride, P.c_off, row_idx, table, types);
+  else
+    gemm_split_store<NT, 1>(acc, rows, row0, half, li, tile0, C, n_rows, N, c_node_stride, P.c_off, row_idx, 0);
+}
+
+__global__ __launch_bounds__(256, SNET_GEMM_OCC) void gemm_multi_kernel(MultiArgs G, float *__restrict__ C, int64_t n_nodes,
+                                                                        int64_t c_node_stride, const int32_t *__restrict__ row_idx,
+                                                                        const float *__restrict__ table,
+                                                                        const int32_t *__restrict__ types) {
+  __shared__ snet::u32x4 Bs[2 * 4 * 192];
+  int q = 0;
+  while (q + 1 < G.n && (int)blockIdx.x >= G.first_block[q + 1]) ++q;
+  const MultiProb P = G.p[q];
+  const int b = blockIdx.x - G.first_block[q];
+  const int by = b % G.nby[q], bx = b / G.nby[q];   // the column blocks of a row block are neighbours: they share its A rows
+  const int64_t n_rows = n_nodes * P.d;
+  if (P.s[1].nq > 0) {   // two sources: two accumulator sets, tiles of at most 64 columns
+    if (P.N > 32)
+      gemm_multi_body<2, 2>(Bs, bx, by, P, C, n_rows, c_node_stride, row_idx, table, types);
+    else
+      gemm_multi_body<1, 2>(Bs, bx, by, P, C, n_rows, c_node_stride, row_idx, table, types);
+  } else if (P.N > 64)
+    gemm_multi_body<4, 1>(Bs, bx, by, P, C, n_rows, c_node_stride, row_idx, table, types);
+  else if (P.N > 32)
+    gemm_multi_body<2, 1>(Bs, bx, by, P, C, n_rows, c_node_stride, row_idx, table, types);
+  else
+    gemm_multi_body<1, 1>(Bs, bx, by, P, C, n_rows, c_node_stride, row_idx, table, types);
+}
+
 inline uint16_t bf16_rne(float v) {
   uint32_t u;
   memcpy(&u, &v, 4);
@@ -535,6 +773,56 @@ extern "C" int snet_gemm_grouped(const snet_gemm_desc *descs_host, int32_t n_des
   else
     gemm_split_grouped_kernel<1><<<(unsigned)total, 256, 0, st>>>(G, A, C, n_nodes, a_node_stride, c_node_stride, row_idx);
   SNET_CHECK_LAUNCH("snet_gemm_grouped");
+  return 0;
+}
+
+extern "C" int snet_gemm_multi(const snet_gemm_multi_desc *descs_host, int32_t n_desc, float *C, int64_t n_nodes,
+                               int64_t c_node_stride, const int32_t *row_idx, const float *table, const int32_t *types,
+                               void *stream) {
+  SNET_REQUIRE(descs_host != nullptr && n_desc >= 1 && n_desc <= SNET_MAX_GEMM_GROUP, "snet_gemm_multi: 1..8 problems required");
+  if (n_nodes <= 0) return 0;
+  SNET_REQUIRE(C != nullptr && (table == nullptr) == (types == nullptr), "snet_gemm_multi: bad argument (C, table without types)");
+  MultiArgs G;
+  G.n = n_desc;
+  int64_t total = 0;
+  int n_src = 0, n_split = 0;
+  for (int i = 0; i < n_desc; ++i) {
+    const snet_gemm_multi_desc &p = descs_host[i];
+    SNET_REQUIRE(p.n_src >= 1 && p.n_src <= SNET_GEMM_MAX_SRC, "snet_gemm_multi: one or two sources per problem");
+    SNET_REQUIRE(p.d >= 1 && p.d <= 150 && p.N >= 1, "snet_gemm_multi: bad problem (1 <= d <= 150)");
+    for (int e = 0; e < p.n_src; ++e) {
+      const snet_gemm_src &s = p.src[e];
+      SNET_REQUIRE(s.A != nullptr && s.K >= 1 && (s.B != nullptr || s.B_split != nullptr), "snet_gemm_multi: bad source");
+      SNET_REQUIRE(snet_gemm_split_size(s.K, p.N) < (1ll << 32), "snet_gemm_multi: weight block too large");   // (32-bit byte offsets)
+      ++n_src;
+      n_split += s.B_split != nullptr && s.B == nullptr;
+    }
+  }
+  SNET_REQUIRE(n_split == 0 || n_split == n_src, "snet_gemm_multi: mix of split-packed and fp32 weights in one launch");
+  SNET_REQUIRE(n_split == n_src, "snet_gemm_multi: split-packed weights only (fp32 weights: snet_gemm_grouped)");
+  for (int i = 0; i < n_desc; ++i) {
+    const snet_gemm_multi_desc &p = descs_host[i];
+    MultiProb &P = G.p[i];
+    for (int e = 0; e < 2; ++e) {   // (a one-source problem: source 1 = source 0 with no k steps, see MultiProb)
+      const snet_gemm_src &s = p.src[e < p.n_src ? e : 0];
+      P.s[e] = {s.A, static_cast<const snet::u32x4 *>(s.B_split), s.a_node_stride, s.a_off, s.K, e < p.n_src ? (s.K + 15) / 16 : 0};
+    }
+    P.c_off = p.c_off;
+    P.d = p.d;
+    P.N = p.N;
+    const int bn = (p.N > 64 && p.n_src == 1) ? 128 : (p.N > 32 ? 64 : 32);   // (two accumulator sets: tiles of at most 64 columns)
+    const int64_t nbx = (n_nodes * p.d + 127) / 128;
+    const int64_t nby = (p.N + bn - 1) / bn;
+    SNET_REQUIRE(nbx < (1ll << 30), "snet_gemm_multi: too many rows");
+    G.nby[i] = (int)nby;
+    G.first_block[i] = (int)total;
+    total += nbx * nby;
+  }
+  G.first_block[n_desc] = (int)total;
+  SNET_REQUIRE(total < (1ll << 31), "snet_gemm_multi: grid too large");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  gemm_multi_kernel<<<(unsigned)total, 256, 0, st>>>(G, C, n_nodes, c_node_stride, row_idx, table, types);
+  SNET_CHECK_LAUNCH("snet_gemm_multi");
   return 0;
 }
 

@@ -5,6 +5,7 @@
 // (sevennet_amd/engine.py), no torch, no Python.  Ghost-feature exchange is left to the host through
 // two callbacks invoked at the reference's exchange points (pair_e3gnn_parallel.cpp:369,435).
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -120,7 +121,102 @@ void plan_groups(Linear &L, bool transpose) {
     written.push_back({tgt, b.species});
   }
 }
+
+// out = sum_i linears[i](a_i), every row written once (snet_gemm_multi): forward [SI2, sc] onto y, reverse [sc, SI1] onto g_x,
+// [SI2] alone for layer 0's launch that adds the species table's row.  The same rule, loop for loop, as the Python host
+// (model_spec.py::plan_multi_source): one launch per row list (species 0 .. n_species-1 when a linear has per-species weights, else
+// all rows), one problem per output block in the order the blocks first appear, its sources in the order of the linears.
+// ok = false where the rule does not apply; the sequencer then keeps the write-then-accumulate launches.
+struct MultiPlan {
+  struct Launch {
+    int species;
+    std::vector<snet_gemm_multi_desc> descs;   // (src[e].A is set per call)
+    std::vector<std::array<int, SNET_GEMM_MAX_SRC>> which;   // per problem and source: the linear that feeds it
+  };
+  bool ok = false;
+  bool transpose = false;
+  int dim = 0;
+  std::vector<const float *> bias;   // the linears' constant rows (device, null where a linear has none), in the order given
+  std::vector<Launch> launches;
+  std::vector<std::pair<int, int>> zero;   // output column ranges no problem writes
+};
+
+void plan_multi_source(MultiPlan &P, std::vector<const Linear *> linears, bool transpose) {
+  P = MultiPlan();
+  P.transpose = transpose;
+  for (const Linear *L : linears) P.bias.push_back(L->bias);
+  if (linears.empty() || linears.size() > SNET_GEMM_MAX_SRC) return;
+  int ns = 0;
+  P.dim = transpose ? linears[0]->dim_in : linears[0]->dim_out;
+  for (const Linear *L : linears) {
+    if ((transpose ? L->dim_in : L->dim_out) != P.dim) return;
+    if (L->n_species > 0) {
+      if (ns > 0 && ns != L->n_species) return;
+      ns = L->n_species;
+    }
+  }
+  for (auto &z : transpose ? linears[0]->zero_in : linears[0]->zero) {   // untouched by every linear
+    bool all = true;
+    for (size_t i = 1; i < linears.size(); ++i) {
+      bool found = false;
+      for (auto &y : transpose ? linears[i]->zero_in : linears[i]->zero) found |= (y == z);
+      all &= found;
+    }
+    if (all) P.zero.push_back(z);
+  }
+  std::sort(P.zero.begin(), P.zero.end());
+  for (int s = ns > 0 ? 0 : -1; s < (ns > 0 ? ns : 0); ++s) {
+    MultiPlan::Launch la;
+    la.species = s;
+    for (size_t i = 0; i < linears.size(); ++i)
+      for (const Block &b : linears[i]->blocks) {
+        if (b.species != -1 && b.species != s) continue;
+        const int tgt = transpose ? b.in_off : b.out_off, n = transpose ? b.mul_in : b.mul_out, d = 2 * b.l + 1;
+        size_t k = 0;
+        while (k < la.descs.size() && la.descs[k].c_off != tgt) ++k;
+        if (k == la.descs.size()) {
+          snet_gemm_multi_desc nd;
+          memset(&nd, 0, sizeof nd);
+          nd.c_off = tgt;
+          nd.d = d;
+          nd.N = n;
+          la.descs.push_back(nd);
+          la.which.push_back({});
+        }
+        snet_gemm_multi_desc &p = la.descs[k];
+        if (p.d != d || p.N != n || p.n_src >= SNET_GEMM_MAX_SRC) return;
+        for (int e = 0; e < p.n_src; ++e)
+          if (la.which[k][e] == (int)i) return;
+        snet_gemm_src &src = p.src[p.n_src];
+        src.B_split = transpose ? b.WT : b.W;
+        src.a_node_stride = transpose ? linears[i]->dim_out : linears[i]->dim_in;
+        src.a_off = transpose ? b.out_off : b.in_off;
+        src.K = transpose ? b.mul_out : b.mul_in;
+        la.which[k][p.n_src++] = (int)i;
+      }
+    std::vector<char> covered((size_t)P.dim, 0);
+    auto cover = [&](int64_t off, int64_t len) {
+      if (off < 0 || off + len > P.dim) return false;
+      for (int64_t c = off; c < off + len; ++c) {
+        if (covered[c]) return false;
+        covered[c] = 1;
+      }
+      return true;
+    };
+    for (auto &p : la.descs)
+      if (!cover(p.c_off, (int64_t)p.d * p.N)) return;
+    for (auto &z : P.zero)
+      if (!cover(z.first, z.second)) return;
+    for (char c : covered)
+      if (!c) return;
+    if (la.descs.empty() || la.descs.size() > SNET_MAX_GEMM_GROUP) return;
+    P.launches.push_back(std::move(la));
+  }
+  P.ok = true;
+}
+
 struct Layer {
+  MultiPlan fwd2, rev2, fwd_tab;   // y = SI2(m) + sc(x); g_x = sc^T(g_y) + SI1^T(g_h); layer 0: y = SI2(m) + sc0_table[type]
   int dx, dmid, gin, dout, wn;
   char tag[13];
   float conv_scale;
@@ -344,6 +440,39 @@ int run_linear(snet_model *m, const Linear &L, const float *x, float *y, int64_t
   return 0;
 }
 
+// out[:n] = sum_i linear_i(a[i][:n]) (+ table[types]), every row written once: one two-source launch per row list
+// (engine.py::_linear_multi: same launches, same order)
+int run_multi(snet_model *m, MultiPlan &P, const float *a0, const float *a1, float *out, int64_t n, const float *table,
+              const int32_t *types, hipStream_t st) {
+  if (n <= 0) return 0;
+  for (auto &z : P.zero)
+    if (hipMemset2DAsync(out + z.first, (size_t)P.dim * 4, 0, (size_t)z.second * 4, (size_t)n, st) != hipSuccess) {
+      snet::set_error("snet_model_eval: memset failed");
+      return 1;
+    }
+  const float *a[SNET_GEMM_MAX_SRC] = {a0, a1};
+  for (MultiPlan::Launch &la : P.launches) {
+    const int32_t *rows = nullptr;
+    int64_t cnt = n;
+    if (la.species >= 0) {
+      cnt = m->species_cnt[la.species];
+      rows = m->species_rows + m->species_off[la.species];
+      if (cnt == 0) continue;
+    }
+    for (size_t k = 0; k < la.descs.size(); ++k)
+      for (int e = 0; e < la.descs[k].n_src; ++e) la.descs[k].src[e].A = a[la.which[k][e]];
+    const int rc = snet_gemm_multi(la.descs.data(), (int)la.descs.size(), out, cnt, P.dim, rows, table, table ? types : nullptr, st);
+    if (rc) return rc;
+  }
+  if (!P.transpose)   // constant rows stay launches of their own, in the order the separate linears added them
+    for (size_t i = P.bias.size(); i-- > 0;)
+      if (P.bias[i]) {
+        const int rc = snet_add_row_bias(out, P.bias[i], n, P.dim, st);
+        if (rc) return rc;
+      }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int snet_model_load_memory(const void *blob, int64_t n_bytes, snet_model **out) {
@@ -415,6 +544,15 @@ extern "C" int snet_model_load_memory(const void *blob, int64_t n_bytes, snet_mo
       }
     }
     good = good && read_linear(r, L.sc) && read_linear(r, L.si1) && read_linear(r, L.si2);
+    if (good && L.sc.present()) {   // two-source launches (the plans hold device pointers only: L is copied into m->layers below)
+      if (t == 0) {
+        plan_multi_source(L.fwd_tab, {&L.si2}, false);
+        if (!L.fwd_tab.zero.empty()) L.fwd_tab.ok = false;   // the table's row reaches only columns some problem writes
+      } else {
+        plan_multi_source(L.fwd2, {&L.si2, &L.sc}, false);
+        plan_multi_source(L.rev2, {&L.sc, &L.si1}, true);
+      }
+    }
     if (good) {
       const int ns = r.i32();
       good = r.ok && ns >= 1 && ns <= SNET_MAX_GATE_SEGS;
@@ -1035,14 +1173,17 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     A.off = mark;
     float *sc = nullptr;
     float *h = saved[t].h;
+    // the self-connection: its own launch (the rows SI2 then accumulates onto) only where the two-source launch after the
+    // convolution does not apply
+    const bool merged_y = t == 0 ? L.fwd_tab.ok : L.fwd2.ok;
     if (t == 0) {  // species-only inputs: table lookups (ghost rows included)
-      if (L.sc.present()) {
+      if (L.sc.present() && !merged_y) {
         sc = saved[t].y;
         if ((rc = snet_embed_rows(m->sc0_table, types, sc, N, L.gin, st))) return rc;
       }
       if ((rc = snet_embed_rows(m->h0_table, types, h, NT, L.dx, st))) return rc;
     } else {
-      if (L.sc.present()) {
+      if (L.sc.present() && !merged_y) {
         sc = saved[t].y;
         if ((rc = run_linear(m, L.sc, x, sc, N, false, false, st))) return rc;
       }
@@ -1082,7 +1223,13 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         return rc;
     }
     float *y = saved[t].y;   // (sc == y when the layer has a self-connection: SI2 accumulates into its rows, as engine.py does)
-    if ((rc = run_linear(m, L.si2, mid, y, N, false, sc != nullptr, st))) return rc;
+    // -- or, the usual case, y = SI2(m) + sc(x) (layer 0: + the species table's row) written once by one launch per row list
+    if (merged_y)
+      rc = t == 0 ? run_multi(m, L.fwd_tab, mid, nullptr, y, N, m->sc0_table, types, st)
+                  : run_multi(m, L.fwd2, mid, x, y, N, nullptr, nullptr, st);
+    else
+      rc = run_linear(m, L.si2, mid, y, N, false, sc != nullptr, st);
+    if (rc) return rc;
     if ((rc = snet_gate_fwd(y, nullptr, x2, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(), st))) return rc;
     std::swap(x, x2);
   }
@@ -1146,6 +1293,13 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     }
   }
   const size_t mark2 = A.off;
+  // g_x = sc^T g_y + SI1^T g_h once the ghost rows of g_h are complete: ONE two-source launch per row list that writes g_x, or --
+  // where that does not apply -- SI1^T g_h accumulated onto the rows sc^T g_y wrote before (in THIS order in every branch and in
+  // engine.py: the order is part of the result's last bits)
+  auto node_gx = [&](Layer &L, const float *g_y, const float *g_h, float *gx) -> int {
+    if (L.rev2.ok) return run_multi(m, L.rev2, g_y, g_h, gx, N, nullptr, nullptr, st);
+    return run_linear(m, L.si1, g_h, gx, N, true, L.sc.present(), st);
+  };
   for (int t = Lc - 1; t >= 0; --t) {
     Layer &L = m->layers[t];
     A.off = mark2;
@@ -1213,11 +1367,11 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
           if ((rc = transposed ? bwd_all() : packed ? bwd_tiles(ptile_e0, ptile_nodes, ptile_k) : bwd_tiles(tile_ptr, tile_node, tile_k))) return rc;
           if ((rc = gh_rows(0, N))) return rc;
           if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, emb, g_h2, E, g_emb, st))) return rc;
-          if (L.sc.present())   // sc^T g_y does not read the ghost gradients: it runs under the exchange too
+          if (L.sc.present() && !L.rev2.ok)   // sc^T g_y does not read the ghost gradients: as a launch of its own it runs under the exchange
             if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
           SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_h1, 0) == hipSuccess, "snet_model_eval: stream ordering failed");
           if ((rc = snet_halo_reverse_accumulate(m->halo_user, g_h, L.dx, st))) return rc;
-          if ((rc = run_linear(m, L.si1, g_h, gx_next, N, true, L.sc.present(), st))) return rc;
+          if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
           std::swap(g_x, gx_next);
           continue;
         }
@@ -1230,9 +1384,9 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, emb, g_h2, E, g_emb, st))) return rc;
         // g_x = sc^T g_y, then SI1^T g_h accumulated onto it -- in THIS order in every branch and in engine.py: an accumulating
         // launch starts its accumulators from the rows already there, so the order is part of the result's last bits
-        if (L.sc.present())
+        if (L.sc.present() && !L.rev2.ok)
           if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
-        if ((rc = run_linear(m, L.si1, g_h, gx_next, N, true, L.sc.present(), st))) return rc;
+        if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
         std::swap(g_x, gx_next);
         continue;
       }
@@ -1264,9 +1418,9 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         return rc;
       }
     // g_x (for the previous layer's gate output) = sc^T g_y + SI1^T g_h (same order as above)
-    if (L.sc.present())
+    if (L.sc.present() && !L.rev2.ok)
       if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
-    if ((rc = run_linear(m, L.si1, g_h, gx_next, N, true, L.sc.present(), st))) return rc;
+    if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
     std::swap(g_x, gx_next);
   }
   for (int b = 0; b < 2; ++b)

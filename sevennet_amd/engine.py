@@ -24,7 +24,8 @@ import torch
 
 from . import _lib
 from .model_spec import (ACT_CST, ACT_ID, LinearSpec, ModelSpec, build_model_spec, folded_readout, lastlayer_merged_eligible,
-                         layer0_moments_eligible,                         linear_modal_bias, linear_weight_matrices, species_only_tables, transposed_scalar_conv)
+                         layer0_moments_eligible,                         linear_modal_bias, linear_weight_matrices, plan_multi_source, species_only_tables,
+                         transposed_scalar_conv)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -275,6 +276,32 @@ class _Linear:
         return out
 
 
+class _MultiPlan:
+    """Launch plan of out = sum_i linears[i](a_i), every row written once (snet_gemm_multi): the descriptor arrays of
+    model_spec.plan_multi_source with the weights filled in; the A pointers are set per call.  `ok` is False where the rule does
+    not apply or the weights are fp32 -- the caller keeps the write-then-accumulate launches."""
+
+    def __init__(self, linears: List[_Linear], transpose: bool):
+        self.linears, self.transpose = linears, transpose
+        plan = plan_multi_source([l.spec for l in linears], transpose) if all(l.split for l in linears) else None
+        self.ok = plan is not None
+        if not self.ok:
+            return
+        self.dim_out = linears[0].spec.dim_in if transpose else linears[0].spec.dim_out
+        self.zero = plan[1]
+        self.launches = []   # (species, GemmMultiDesc array, n, per problem: which linear feeds source e)
+        for species, probs in plan[0]:
+            arr = (_lib.GemmMultiDesc * len(probs))()
+            for p, (c_off, d, n, srcs) in zip(arr, probs):
+                p.c_off, p.n_src, p.d, p.N = c_off, len(srcs), d, n
+                for s, (i, j) in zip(p.src, srcs):
+                    lin, b = linears[i], linears[i].spec.blocks[j]
+                    s.B_split = (lin.wt if transpose else lin.w)[j].data_ptr()
+                    s.a_node_stride = lin.spec.dim_out if transpose else lin.spec.dim_in
+                    s.a_off, s.K = (b.out_off, b.mul_out) if transpose else (b.in_off, b.mul_in)
+            self.launches.append((species, arr, len(probs), [[i for i, _ in srcs] for _, _, _, srcs in probs]))
+
+
 class _Span:
     """HIP-event bracket around one kernel class (bench.py's per-kernel timing)."""
 
@@ -387,6 +414,7 @@ class HipForceEngine:
                 L.sc = _Linear(ls.sc, sd[ls.sc.name], self.dev, split, mi) if ls.sc is not None else None
                 L.si1 = _Linear(ls.si1, sd[ls.si1.name], self.dev, split, mi, sd.get(ls.si1.bias_name))
                 L.si2 = _Linear(ls.si2, sd[ls.si2.name], self.dev, split, mi, sd.get(ls.si2.bias_name))
+                self._plan_two_source(L, first=not self.layers)
                 L.mlp_w, L.mlp_wt = [], []
                 rw = ls.radial_weights(sd)   # last layer restricted to the live paths' columns
                 for i in range(len(ls.mlp_dims) - 1):
@@ -574,6 +602,40 @@ class HipForceEngine:
         if lin.bias is not None and n > 0:
             _lib.check(self.lib.snet_add_row_bias(_ptr(y), _ptr(lin.bias), n, sp.dim_out, _stream()), 'snet_add_row_bias')
         return y
+
+    @staticmethod
+    def _plan_two_source(L, first: bool):
+        """y = SI2(m) + sc(x) and g_x = sc^T(g_y) + SI1^T(g_h) from one two-source launch per row list; the first layer
+        with species tables: y = SI2(m) + sc0_table[type], the row added in the epilogue (every column of y must be a target)"""
+        L.fwd2 = _MultiPlan([L.si2, L.sc], False) if L.sc is not None else None
+        L.rev2 = _MultiPlan([L.sc, L.si1], True) if (L.sc is not None and not first) else None
+        L.fwd_tab = _MultiPlan([L.si2], False) if (L.sc is not None and first) else None
+        if L.fwd_tab is not None and L.fwd_tab.ok and L.fwd_tab.zero:
+            L.fwd_tab.ok = False
+
+    def _linear_multi(self, plan: _MultiPlan, srcs, n, g: Graph, table=None):
+        """out[:n] = sum_i plan.linears[i](srcs[i][:n]) (+ table[types]), each row written once: one launch per row list"""
+        out = self._new(max(n, 0), plan.dim_out)
+        for off, ln in plan.zero:
+            out[:, off:off + ln].zero_()
+        ptrs = [s.data_ptr() for s in srcs]
+        for species, arr, cnt, which in plan.launches:
+            rows, m = None, n
+            if species >= 0:
+                rows = g.species_rows[species]
+                m = rows.numel()
+                if m == 0:
+                    continue
+            for p, w in zip(arr, which):
+                for s, i in zip(p.src, w):
+                    s.A = ptrs[i]
+            _lib.check(self.lib.snet_gemm_multi(arr, cnt, _ptr(out), m, plan.dim_out, _ptr(rows), _ptr(table),
+                                                _ptr(g.types) if table is not None else None, _stream()), 'snet_gemm_multi')
+        if not plan.transpose and n > 0:   # constant rows stay launches of their own, in the order the separate linears added them
+            for lin in reversed(plan.linears):
+                if lin.bias is not None:
+                    _lib.check(self.lib.snet_add_row_bias(_ptr(out), _ptr(lin.bias), n, plan.dim_out, _stream()), 'snet_add_row_bias')
+        return out
 
     def _linear_T(self, lin: _Linear, gy, n, g: Graph, out=None, accumulate=False):
         """g_x[:n] (+)= Linear^T(g_y[:n]).  The first (in,out) pair that reaches an input block
@@ -825,8 +887,14 @@ class HipForceEngine:
                         pending = halo.forward_start(h, N)
                     else:
                         halo.forward(h, N)
+            # the self-connection: its own launch (the rows SI2 then accumulates onto) only where the two-source launch after the
+            # convolution does not apply
+            tab0 = t == 0 and self.h0_table is not None
+            merged_y = (L.fwd_tab is not None and L.fwd_tab.ok and self.sc0_table is not None) if tab0 else (L.fwd2 is not None and L.fwd2.ok)
             with _Span(self, 'node_linear_fwd'):
-                if t == 0 and self.h0_table is not None:
+                if merged_y:
+                    sc = None
+                elif tab0:
                     sc = None
                     if self.sc0_table is not None:
                         sc = self._new(N, ls.gate.irreps_in.dim)
@@ -876,7 +944,12 @@ class HipForceEngine:
             with _Span(self, 'node_linear_fwd'):
                 # y = SI2(m) + self-connection: the linear map ACCUMULATES into the self-connection's rows (the gate kernel used to
                 # add them: one read of sc and one write of y per node and layer more); y is kept for the reverse pass
-                y = self._linear(L.si2, m, N, g) if sc is None else self._linear(L.si2, m, N, g, out=sc, accumulate=True)
+                # -- or, the usual case, y = SI2(m) + sc(x) (layer 0: + the species table's row) from ONE launch per row list: both
+                # products are formed in the launch, added at the store, and y is written once (snet_gemm_multi; same bits)
+                if merged_y:
+                    y = self._linear_multi(L.fwd_tab, [m], N, g, table=self.sc0_table) if tab0 else self._linear_multi(L.fwd2, [m, x], N, g)
+                else:
+                    y = self._linear(L.si2, m, N, g) if sc is None else self._linear(L.si2, m, N, g, out=sc, accumulate=True)
             xo = self._new(N, ls.gate.irreps_out.dim)
             with _Span(self, 'gate_fwd'):
                 _lib.check(lib.snet_gate_fwd(_ptr(y), None, _ptr(xo), N, ls.gate.irreps_in.dim,
@@ -1123,13 +1196,20 @@ class HipForceEngine:
                 break
             # g_x = sc^T g_y + SI1^T g_h: the self-connection's share does not need the ghost gradients, so it runs
             # while they travel (reverse_start above put the exchange on the halo's stream)
-            with _Span(self, 'node_linear_bwd'):
-                g_x = self._linear_T(L.sc, g_y, N, g) if L.sc is not None else None
+            # -- where the two-source launch does not apply.  Otherwise ONE launch writes g_x from both products, after the ghost
+            # gradients have landed in g_h
+            merged_gx = L.rev2 is not None and L.rev2.ok
+            if not merged_gx:
+                with _Span(self, 'node_linear_bwd'):
+                    g_x = self._linear_T(L.sc, g_y, N, g) if L.sc is not None else None
             if pending is not None:
                 with _Span(self, 'halo_rev'):
                     halo.reverse_finish(pending, g_h)
             with _Span(self, 'node_linear_bwd'):
-                g_x = self._linear_T(L.si1, g_h, N, g, out=g_x, accumulate=g_x is not None)
+                if merged_gx:
+                    g_x = self._linear_multi(L.rev2, [g_y, g_h], N, g)
+                else:
+                    g_x = self._linear_T(L.si1, g_h, N, g, out=g_x, accumulate=g_x is not None)
             saved[t] = None
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)

@@ -176,6 +176,73 @@ def linear_weight_matrices(spec: LinearSpec, flat: np.ndarray):
     return out
 
 
+MAX_GEMM_GROUP = 8   # == SNET_MAX_GEMM_GROUP
+MAX_GEMM_SRC = 2     # == SNET_GEMM_MAX_SRC
+
+
+def linear_untouched(spec: LinearSpec, transpose: bool):
+    """(offset, length) column ranges of a linear's output side no block writes: `zero_out`, or -- for the transposed map, whose
+    output side is the linear's input -- the input blocks no block reads"""
+    if not transpose:
+        return list(spec.zero_out)
+    fed = {b.in_off for b in spec.blocks}
+    return [(off, m * (2 * l + 1)) for off, (m, l, _) in zip(spec.irreps_in.offsets(), spec.irreps_in) if off not in fed]
+
+
+def plan_multi_source(linears, transpose: bool):
+    """Launch lists of  out = sum_i linears[i](a_i)  with every output row written ONCE (snet_gemm_multi): forward
+    [SI2, sc] onto y, reverse (transpose=True) [sc, SI1] onto g_x, or [SI2] alone for the launch that adds the species table row.
+    THE grouping rule of both hosts (snet_model.cpp::plan_multi_source is the same loop).
+
+    One launch per row list: species s = 0 .. n_species-1 when a linear has per-species weights (shared blocks, species -1, then run
+    over each list with the same weights; the lists cover every local row once), else the single list -1 of all rows.  Within a
+    list, one problem per output block, in the order the blocks first appear (linears in the order given, blocks in spec order); a
+    problem's sources are the blocks that write it, same order.
+    -> (launches, zero) with launches = [(species, [(c_off, d, N, [(i, block index), ...]), ...])] and zero = [(off, len)] the
+    output column ranges no problem writes (to be zero-filled); or None where the rule does not apply -- an output block with two
+    blocks of one linear or with more than MAX_GEMM_SRC sources, blocks of one target that disagree in (d, N), more than
+    MAX_GEMM_GROUP problems in a list, linears that disagree in their output side -- and the caller keeps the write-then-accumulate
+    launches."""
+    assert 1 <= len(linears) <= MAX_GEMM_SRC
+    dim = {(sp.dim_in if transpose else sp.dim_out) for sp in linears}
+    ns = {sp.n_species for sp in linears if sp.n_species}
+    if len(dim) != 1 or len(ns) > 1:
+        return None
+    dim = dim.pop()
+    zero = set(linear_untouched(linears[0], transpose))
+    for sp in linears[1:]:
+        zero &= set(linear_untouched(sp, transpose))
+    zero = sorted(zero)
+    launches = []
+    for s in (range(ns.pop()) if ns else (-1,)):
+        probs, by_tgt = [], {}
+        for i, sp in enumerate(linears):
+            for j, b in enumerate(sp.blocks):
+                if b.species not in (-1, s):
+                    continue
+                tgt, n = (b.in_off, b.mul_in) if transpose else (b.out_off, b.mul_out)
+                if tgt not in by_tgt:
+                    by_tgt[tgt] = len(probs)
+                    probs.append((tgt, 2 * b.l + 1, n, []))
+                _, d, n0, src = probs[by_tgt[tgt]]
+                if (d, n0) != (2 * b.l + 1, n) or any(i_ == i for i_, _ in src):
+                    return None
+                src.append((i, j))
+        covered = np.zeros(dim, bool)
+        for off, d, n, _ in probs:
+            if off + d * n > dim or covered[off:off + d * n].any():
+                return None
+            covered[off:off + d * n] = True
+        for off, ln in zero:
+            if covered[off:off + ln].any():
+                return None
+            covered[off:off + ln] = True
+        if not probs or len(probs) > MAX_GEMM_GROUP or not covered.all():
+            return None
+        launches.append((s, probs))
+    return launches, zero
+
+
 def linear_rows_fp64(spec: LinearSpec, flat: np.ndarray, x: np.ndarray, species=None, modal_idx: int = -1, bias_flat=None) -> np.ndarray:
     """y = Linear(x) for ir_mul rows x[n, dim_in], evaluated in fp64 on the host (load time only).
     species[n] selects the weight slice of a per-species (FCTP) linear."""
