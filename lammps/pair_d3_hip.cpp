@@ -106,10 +106,16 @@ double PairD3Hip::init_one(int i, int j) {
 
 // energy, forces, virial of the whole periodic cell held by this process            (pair_d3.cu:1970-2021)
 void PairD3Hip::compute(int eflag, int vflag) {
-  if (eflag || vflag)   // (the reference's own idiom, pair_e3gnn.cpp:80-83 / pair_d3.cu:2000)
+  // What stock Pair::ev_init does.  The branches below read the flag MEMBERS, which only ev_setup writes: on a step without
+  // flags (almost every MD step) they must not keep the values of the last thermo / dump step -- the energy and virial would be
+  // added again, and eatom / vatom, sized by that step's ev_setup, written for the nall of this one.
+  if (eflag || vflag) {
     ev_setup(eflag, vflag);
-  else
+  } else {   // = Pair::ev_unset
     evflag = vflag_fdotr = 0;
+    eflag_either = eflag_global = eflag_atom = 0;
+    vflag_either = vflag_global = vflag_atom = 0;
+  }
   const int n = (int)atom->natoms;
   if (n != atom->nlocal) error->all(FLERR, "pair_style d3 is a one-process style (like the reference's CUDA version)");
   xflat.resize((size_t)n * 3);

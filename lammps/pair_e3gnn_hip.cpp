@@ -208,10 +208,16 @@ void PairE3GNNHip::build_halo_plan() {
 }
 
 void PairE3GNNHip::compute(int eflag, int vflag) {
-  if (eflag || vflag)   // (the reference's own idiom, pair_e3gnn.cpp:80-83 / pair_d3.cu:2000)
+  // What stock Pair::ev_init does.  The branches below read the flag MEMBERS, which only ev_setup writes: on a step without
+  // flags (almost every MD step) they must not keep the values of the last thermo / dump step -- the energy and virial would be
+  // added again, and eatom / vatom, sized by that step's ev_setup, written for the nall of this one.
+  if (eflag || vflag) {
     ev_setup(eflag, vflag);
-  else
+  } else {   // = Pair::ev_unset
     evflag = vflag_fdotr = 0;
+    eflag_either = eflag_global = eflag_atom = 0;
+    vflag_either = vflag_global = vflag_atom = 0;
+  }
   if (ghost_mode == 1 && vflag_atom) error->all(FLERR, "atomic stress is not supported\n");
   // an empty sub-domain: the reference's parallel style fails inside LibTorch there (docs/source/user_guide/lammps_torch.md:
   // 111-113: "encounters an error when one of the subdomain cells contains no atoms"); this one stops with a message that names

@@ -72,18 +72,42 @@ void Pair::ev_setup(int eflag, int vflag, int /*alloc*/) {
   eng_vdwl = eng_coul = 0.0;
   for (double &v : virial) v = 0.0;
   const int nall = atom->nlocal + atom->nghost;
+  // (mock) each array ends in a guard band of PairProbe::GUARD_DOUBLES doubles, see pair.h
+  const auto guarded = [](size_t n) {
+    double *p = static_cast<double *>(std::calloc(n + PairProbe::GUARD_DOUBLES, sizeof(double)));
+    const unsigned long long bits = PairProbe::GUARD_BITS;
+    for (int k = 0; k < PairProbe::GUARD_DOUBLES; ++k) std::memcpy(p + n + k, &bits, sizeof bits);
+    return p;
+  };
   if (eflag_atom) {
-    if (maxeatom < nall) { std::free(eatom); eatom = static_cast<double *>(std::calloc((size_t)nall + 1, sizeof(double))); maxeatom = nall; }
+    if (maxeatom < nall) { std::free(eatom); eatom = guarded((size_t)nall); maxeatom = nall; }
     std::memset(eatom, 0, sizeof(double) * (size_t)nall);
   }
   if (vflag_atom) {
     if (maxvatom < nall) {
       if (vatom) { std::free(vatom[0]); std::free(vatom); }
-      memory->create(vatom, nall, 6, "pair:vatom");
+      double *data = guarded((size_t)nall * 6);
+      vatom = static_cast<double **>(std::malloc(sizeof(double *) * (size_t)(nall > 0 ? nall : 1)));
+      vatom[0] = data;
+      for (int i = 0; i < nall; ++i) vatom[i] = data + (size_t)i * 6;
       maxvatom = nall;
     }
     std::memset(vatom[0], 0, sizeof(double) * 6 * (size_t)nall);
   }
+}
+
+void PairProbe::flags(const Pair &p, int out[8]) {
+  const int v[8] = {p.eflag_either, p.eflag_global, p.eflag_atom, p.vflag_either, p.vflag_global, p.vflag_atom, p.evflag, p.vflag_fdotr};
+  std::memcpy(out, v, sizeof v);
+}
+bool PairProbe::guard_ok(const Pair &p) {
+  const auto band_ok = [](const double *end) {
+    const unsigned long long bits = GUARD_BITS;
+    for (int k = 0; k < GUARD_DOUBLES; ++k)
+      if (std::memcmp(end + k, &bits, sizeof bits) != 0) return false;
+    return true;
+  };
+  return (!p.eatom || band_ok(p.eatom + p.maxeatom)) && (!p.vatom || band_ok(p.vatom[0] + (size_t)p.maxvatom * 6));
 }
 
 }  // namespace LAMMPS_NS
@@ -98,6 +122,7 @@ int MPI_Alltoall(const void *sendbuf, int sendcount, MPI_Datatype sendtype, void
 int MPI_Alltoallv(const void *sendbuf, const int *sendcounts, const int *sdispls, MPI_Datatype sendtype, void *recvbuf,
                   const int *, const int *rdispls, MPI_Datatype, MPI_Comm) {
   const size_t sz = mock_type_size(sendtype);
+  if (sendcounts[0] == 0) return 0;   // (empty vectors hand over null pointers)
   std::memcpy(static_cast<char *>(recvbuf) + (size_t)rdispls[0] * sz, static_cast<const char *>(sendbuf) + (size_t)sdispls[0] * sz,
               (size_t)sendcounts[0] * sz);
   return 0;

@@ -33,5 +33,17 @@ class Pair : protected Pointers {
   void ev_setup(int eflag, int vflag, int alloc = 1);
   int evflag = 0, vflag_fdotr = 0;
   int maxeatom = 0, maxvatom = 0;
+  friend struct PairProbe;   // (mock only) the scripted driver reads the flags and checks the guard bands
+};
+
+// (mock only) ev_setup allocates eatom / vatom with GUARD_DOUBLES doubles of GUARD_BITS behind their end: a style that writes
+// per-atom values past the size of the last ev_setup lands there first, and the driver sees it without a sanitizer
+struct PairProbe {
+  static constexpr int GUARD_DOUBLES = 64;
+  static constexpr unsigned long long GUARD_BITS = 0xA5A5A5A5A5A5A5A5ull;
+  static void flags(const Pair &p, int out[8]);   // eflag_either, _global, _atom, vflag_either, _global, _atom, evflag, vflag_fdotr
+  static int maxeatom(const Pair &p) { return p.maxeatom; }
+  static int maxvatom(const Pair &p) { return p.maxvatom; }
+  static bool guard_ok(const Pair &p);
 };
 }  // namespace LAMMPS_NS

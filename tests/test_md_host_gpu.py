@@ -59,7 +59,9 @@ class MdHost:
         self.lib.snet_md_destroy(self.h)
 
     def compute(self, x, tag, nlocal, rows, types, ghost_mode=0, ilist=None, tag_bytes=4, eflag_atom=1, vflag_atom=1,
-                special_bits=False, unchanged=False):
+                special_bits=False, unchanged=False, vflag=1, sentinel=None):
+        """sentinel: every output that is NOT requested (virial without vflag, eatom without eflag_atom, vatom without vflag_atom)
+        is filled with it and still handed to the library, so that a write to it shows"""
         from sevennet_amd import _lib
         if unchanged:   # what the pair style does when neighbor->ago > 0
             _lib.check(self.lib.snet_md_list_unchanged(self.h), 'snet_md_list_unchanged')
@@ -81,12 +83,17 @@ class MdHost:
         tmap = np.arange(-1, ntypes, dtype=np.int32)    # type t -> species t-1
         f = np.zeros((nall, 3)); eng = C.c_double(0.0); vir = np.zeros(6)
         eatom = np.zeros(nall); vatom = np.zeros((nall, 6))
+        if sentinel is not None:
+            for arr, wanted in ((vir, vflag), (eatom, eflag_atom), (vatom, vflag_atom)):
+                if not wanted:
+                    arr.fill(sentinel)
         n2a = np.full(nall, -1, np.int32)
         nn, ne = C.c_int64(), C.c_int64()
         P = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
         rc = self.lib.snet_md_compute(self.h, len(ilist), P(ilist), P(numneigh), C.cast(first, C.c_void_p), nall, P(x), P(ty),
-                                      P(tg), tag_bytes, P(tmap), ntypes, ghost_mode, eflag_atom, 1, vflag_atom, P(f),
-                                      C.cast(C.byref(eng), C.c_void_p), P(vir), P(eatom), P(vatom) if vflag_atom else None,
+                                      P(tg), tag_bytes, P(tmap), ntypes, ghost_mode, eflag_atom, vflag, vflag_atom, P(f),
+                                      C.cast(C.byref(eng), C.c_void_p), P(vir), P(eatom),
+                                      P(vatom) if vflag_atom or sentinel is not None else None,
                                       P(n2a), C.byref(nn), C.byref(ne), C.c_void_p(torch.cuda.current_stream().cuda_stream))
         _lib.check(rc, 'snet_md_compute')
         return dict(f=f, energy=eng.value, virial=vir, eatom=eatom, vatom=vatom, node_to_atom=n2a[:nn.value],
@@ -200,6 +207,36 @@ def test_md_host_rejects_bad_input():
         host.compute(x, tag, nlocal, rows, np.asarray(types)[tag - 1], ghost_mode=3)
     with pytest.raises(RuntimeError, match='atomic stress'):
         host.compute(x, tag, nlocal, rows, np.asarray(types)[tag - 1], ghost_mode=1)
+
+
+def test_md_host_outputs_switched_off_leave_the_others_and_the_forces_unchanged():
+    """snet_md_compute over all eight (eflag_atom, vflag, vflag_atom): every ordinary MD step of a LAMMPS run is (0, 0, 0), which no
+    other test runs.  Forces and energy are bit-identical across all eight, every requested output equals the all-on run bit for
+    bit, every output that was not requested still holds the sentinel it was pre-filled with; per-atom stress with ghost nodes is
+    refused with the library's message whatever else is asked."""
+    import itertools
+    cfg, sd, cutoff, types, pos, cell, ei, ev = _setup('unit')
+    n = len(types)
+    x, tag, nlocal, rows = lammps_domain(pos, cell, np.ones(n, bool), cutoff + SKIN)
+    ty_all = np.asarray(types)[tag - 1]
+    host = MdHost(cfg, sd)
+    SENTINEL = -1234.5
+    full = host.compute(x, tag, nlocal, rows, ty_all, eflag_atom=1, vflag=1, vflag_atom=1, sentinel=SENTINEL)
+    assert np.abs(full['f'][:n]).max() > 1e-3 and np.abs(full['virial']).max() > 1e-3 and np.abs(full['vatom'][:n]).max() > 1e-6
+    assert not (full['eatom'] == SENTINEL).any() and not (full['vatom'] == SENTINEL).any()
+    for ea, vf, va in itertools.product((0, 1), repeat=3):
+        out = host.compute(x, tag, nlocal, rows, ty_all, eflag_atom=ea, vflag=vf, vflag_atom=va, sentinel=SENTINEL)
+        which = (ea, vf, va)
+        assert np.array_equal(out['f'], full['f']) and out['energy'] == full['energy'], which
+        assert out['n_edges'] == full['n_edges'] and out['n_nodes'] == full['n_nodes'], which
+        for key, wanted in (('eatom', ea), ('virial', vf), ('vatom', va)):
+            if wanted:
+                assert np.array_equal(out[key], full[key]), (which, key)
+            else:
+                assert (out[key] == SENTINEL).all(), (which, key)
+    for ea, vf in itertools.product((0, 1), repeat=2):
+        with pytest.raises(RuntimeError, match='atomic stress is not supported with ghost nodes'):
+            host.compute(x, tag, nlocal, rows, ty_all, ghost_mode=1, eflag_atom=ea, vflag=vf, vflag_atom=1, sentinel=SENTINEL)
 
 
 class _TwoRankHalo:
