@@ -95,33 +95,10 @@ def fused_reference(spec, x, sh, dsh, h2, W2, w_row, row_ptr, src, scale, g_out,
     """fp64 reference of the fused operation on engine (ir_mul) rows: w = h2[w_row] W2 -> uvu tensor product -> segment sum, and its
     gradients by autograd.  Returns out[N, dout], the per-edge messages msg[E, dout] (out = their sum per destination row),
     g_xe[E, dx], g_h2[E, 64] = g_w W2^T, the spherical part of g_vec[E, 3] = dE/dY . dsh (Y_0 is constant: its Jacobian row is not
-    read) and, given h2' rows, the radial scalar g_rad[E] = sum_k g_w[e, k] (h2' W2)[k]."""
-    from oracle.e3 import Irreps as OIrreps
-    from oracle.model import tp_uvu
-    from sevennet_amd.irreps import irmul_to_mulir_index, mulir_to_irmul_index
-    from test_ops_gpu import _mid_index
-    f64 = torch.float64
-    N, E, nsh = row_ptr.numel() - 1, src.numel(), sh.shape[1]
-    node = torch.repeat_interleave(torch.arange(N), (row_ptr[1:] - row_ptr[:-1]).long())
-    rows = torch.arange(E) if w_row is None else w_row.long()
-    from_x = torch.as_tensor(irmul_to_mulir_index(spec.irreps_x))
-    to_o = torch.as_tensor(mulir_to_irmul_index(spec.irreps_out))
-    xe = x.to(f64)[src.long()].clone().requires_grad_(True)
-    she = sh.to(f64).clone().requires_grad_(True)
-    h2e = h2.to(f64)[rows].clone().requires_grad_(True)
-    W2 = W2.to(f64)
-    w = h2e @ W2
-    w.retain_grad()
-    ins = [(p.i_x, p.i_sh, k) for p, k in zip(spec.paths, _mid_index(spec))]
-    msg = tp_uvu(xe[:, from_x], she, w, OIrreps(str(spec.irreps_x)), OIrreps(str(spec.irreps_sh)), OIrreps(str(spec.irreps_mid)),
-                 ins)[:, to_o] * scale
-    out = torch.zeros(N, msg.shape[1], dtype=f64).index_add_(0, node, msg)
-    (out * g_out.to(f64)).sum().backward()
-    res = dict(out=out.detach(), msg=msg.detach(), g_xe=xe.grad, g_h2=h2e.grad,
-               g_vec=torch.einsum('ei,eia->ea', she.grad[:, 1:], dsh.to(f64).reshape(E, nsh, 3)[:, 1:]))
-    if h2d is not None:
-        res['g_rad'] = (w.grad * (h2d.to(f64)[rows] @ W2)).sum(1)
-    return res
+    read) and, given h2' rows, the radial scalar g_rad[E] = sum_k g_w[e, k] (h2' W2)[k] -- and what else tests/conv_shapes.conv_reference
+    returns: it is that function, which takes any ConvSpec of the catalogue."""
+    from conv_shapes import conv_reference
+    return conv_reference(spec, x, sh, dsh, w_row, row_ptr, src, scale, g_out, h2=h2, W2=W2, h2d=h2d)
 
 
 def scaled_reference(ref, c, fg, fx, fh, fhd):

@@ -688,19 +688,10 @@ def test_elementwise_node_kernels_beyond_the_grid_cap():
 
 
 def _mid_index(spec):
-    """index of each path's block inside irreps_mid (sorted, one block per path)"""
-    offs = {}
-    out = []
-    # blocks of irreps_mid with the same irrep appear in the order their paths fill the merged block
-    mid = list(spec.irreps_mid)
-    used = [False] * len(mid)
-    order = sorted(range(len(spec.paths)), key=lambda q: (spec.paths[q].out_off, spec.paths[q].out_ch))
-    k = 0
-    idx = [0] * len(spec.paths)
-    for q in order:
-        idx[q] = k
-        k += 1
-    return idx
+    """index of each path's block inside irreps_mid (tests/conv_shapes.mid_index: from the path's out_off / out_ch, so that specs
+    with blocks no path writes work too)"""
+    from conv_shapes import mid_index
+    return mid_index(spec)
 
 
 def test_gate_and_halo_kernels():
