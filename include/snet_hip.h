@@ -711,6 +711,56 @@ int snet_ph_dynmat(const double *phi, const int64_t *p_off, int64_t p_size, cons
                    const int32_t *q_ptr, int32_t n_q, const int64_t *d_off, int32_t n_sys, int32_t max_m, int32_t *status, double *R,
                    double *D, int64_t d_size, double *hermiticity, void *stream);
 
+/* ---- batched elastic tensors from strained copies ---------------------------------------------------
+ * Second-order elastic constants of fully periodic crystals by central differences of the stress over homogeneously strained
+ * copies.  Voigt index j = 0 .. 5 in ASE order (xx, yy, zz, yz, xz, xy), rows are vectors, delta is the strain step.
+ *   Strain patterns: E_j = e_a e_a^T for j < 3 (a = j); E_j = (e_a e_b^T + e_b e_a^T) / 2 for the shears, (a,b) = (1,2), (0,2),
+ *     (0,1) for j = 3, 4, 5, so that a shear step delta is the engineering strain gamma = delta.
+ *   Copy (b, j, q): F = I + (q delta) E_j with s = q delta rounded first (as snet_vib_displace rounds its shift) and h = s 0.5.
+ *     A row x of the positions or of the cell becomes x F:  j < 3:  x_a <- x_a + s x_a;  shear:  x_a <- x_a + h x_b and
+ *     x_b <- x_b + h x_a, both from the unstrained x; the other components are copied.  q = 0 is the unstrained copy, bit for bit.
+ *     q runs over the stencil of snet_vib_rows (-1, +1 for nfree 2; -2, -1, +1, +2 for nfree 4): 6 nfree + 1 copies per system.
+ *   Stress of a copy: sigma_i = -((virial + virial_extra)[p_i] / V'), p = (0, 1, 2, 4, 5, 3) taking the engine's order
+ *     (xx,yy,zz,xy,yz,zx) to ASE Voigt, V' = |det(cell F)| of that copy (computed by the caller on the host, in fp64).
+ *   S[i,j] = d sigma_i / d epsilon_j and L[j, 3 a + k] = d F_ak / d epsilon_j (the internal-strain tensor Lambda at fixed scaled
+ *     coordinates; F the engine's fp32 forces widened, plus forces_extra in fp64) by the same stencil, with f_q the value at q:
+ *       nfree = 2:  (f_+1 - f_-1) / (2 delta)
+ *       nfree = 4:  (((8 f_+1 - f_+2) - 8 f_-1) + f_-2) / (12 delta)
+ *   C = (S + S^T) 0.5 (bitwise symmetric), asymmetry = max |S - S^T|.  Under a residual stress sigma_0 of the unstrained cell S is
+ *     legitimately asymmetric by terms of the order of sigma_0; C is the elastic tensor where that stress is about zero.
+ *   Relaxed ions (on the host, sevennet_amd/elastic.py): with Phi the Gamma Hessian [3n,3n] of the unstrained structure
+ *     (snet_vib_*), T the three normalised uniform translations, P = I - T T^T and kappa the mean diagonal of Phi,
+ *     Phi+ = (P Phi P + kappa T T^T)^-1 - T T^T / kappa and S_rel = S - L Phi+ L^T / V, symmetrised as above.
+ * Every expression is evaluated in fp64 in the order written, no product contracted with a sum, so the results equal the numpy
+ * restatement (tests/elastic_ref.py) bit for bit.  One 256-thread workgroup per unit of work, no atomics, every output element
+ * written by one thread: two runs give identical bits.
+ *
+ * snet_el_strain writes the strained copies.  pos0 / seg_ptr0 / copy_ptr / pos_out / status as snet_vib_displace; copy c is
+ * desc[3 c ..] = (system, j, q) (int32 [n_copies,3]).  A descriptor that does not fit -- a system out of range, j outside 0 .. 5,
+ * |q| > 2, base or output rows outside their arrays, a copy span that differs from the system's atom count -- sets status[c] = 1
+ * (otherwise left as it is) and leaves its rows unwritten; it is refused before anything is read or written.
+ *
+ * snet_el_rows turns the results of the copies of ONE call into columns of S and rows of L.  virial and virial_extra (fp64
+ * [n_copies,6], the latter or NULL), volume (fp64 [n_copies]), forces (fp32 [n_atoms,3]) and forces_extra (fp64 [n_atoms,3] or NULL)
+ * are those of the call's copies, copy c being rows [seg_ptr[c], seg_ptr[c+1]).  Group g is group[3 g ..] = (first copy c0, system b,
+ * column j) (int32 [n_groups,3]): its nfree copies c0 .. c0 + nfree - 1 are adjacent, in the order of the stencil.  System b has
+ * atom_ptr[b+1] - atom_ptr[b] atoms (int32 [n_sys+1], n_base in all); its S is the row-major [6,6] block at S[36 b] (fp64
+ * [36 n_sys]), its L the row-major [6, 3 n_b] block at L[18 atom_ptr[b]] (fp64 [18 n_base]).  Column j of S and row j of L are
+ * WRITTEN, not accumulated, each element once.  A virial, volume or force that is not finite, or a volume that is not positive,
+ * sets status[b] = 2 (int32 [n_sys]); a group that does not fit (copies outside the call or of another size than the system, j
+ * outside 0 .. 5, atoms outside n_base) sets status[b] = 3 and writes nothing else.
+ *
+ * snet_el_finish, once after the last call, one workgroup per system: reads S and writes C (fp64 [36 n_sys]) and asymmetry[b];
+ * both are NaN for a system with status[b] != 0.                                                                              */
+int snet_el_strain(const double *pos0, int64_t n0, const int32_t *seg_ptr0, int32_t n_sys, const int32_t *desc,
+                   const int32_t *copy_ptr, int32_t n_copies, double delta, double *pos_out, int64_t n_out, int32_t *status,
+                   void *stream);
+int snet_el_rows(const double *virial, const double *virial_extra, const double *volume, const float *forces,
+                 const double *forces_extra, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_copies, const int32_t *group,
+                 int32_t n_groups, int32_t nfree, double delta, const int32_t *atom_ptr, int64_t n_base, int32_t n_sys, double *S,
+                 double *L, int32_t *status, void *stream);
+int snet_el_finish(const double *S, int32_t n_sys, const int32_t *status, double *C, double *asymmetry, void *stream);
+
 /* ---- batched NVE / Langevin MD step (fixed cell) -------------------------------------------------
  * One launch per MD step for n_sys systems; units eV, A, fs, amu, with ACC = 9.648533212e-3 (1 eV / (A amu) in A / fs^2).  The
  * atoms of system s are rows [seg_ptr[s], seg_ptr[s+1]) (device int32) of pos / vel (fp64 [n_atoms,3], updated in place), of

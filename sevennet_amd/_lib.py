@@ -178,6 +178,11 @@ SIGNATURES = {
     'snet_ph_dynmat': (C.c_int, [c_f64p, C.c_void_p, C.c_int64, c_f64p, C.c_int64, c_i32p, c_i32p, c_f64p, C.c_int32, c_f64p, c_i32p,
                                  c_i32p, C.c_void_p, C.c_int64, c_f64p, c_i32p, c_i32p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                  c_i32p, c_f64p, c_f64p, C.c_int64, c_f64p, c_stream]),
+    'snet_el_strain': (C.c_int, [c_f64p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_double, c_f64p, C.c_int64, c_i32p,
+                                 c_stream]),
+    'snet_el_rows': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, C.c_int64, c_i32p, C.c_int32, c_i32p, C.c_int32, C.c_int32,
+                               C.c_double, c_i32p, C.c_int64, C.c_int32, c_f64p, c_f64p, c_i32p, c_stream]),
+    'snet_el_finish': (C.c_int, [c_f64p, C.c_int32, c_i32p, c_f64p, c_f64p, c_stream]),
     'snet_mdb_step': (C.c_int, [c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, c_i32p, c_f64p,
                                 C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int32, c_stream]),
     'snet_mdb_init_velocities': (C.c_int, [c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, C.c_uint64, C.c_int32,

@@ -48,9 +48,9 @@ def atoms_velocities(atoms_list, kw: dict) -> dict:
 
 
 class ManyAtomsMixin:
-    """`calculate_many`, `relax_many_atoms`, `neb_many_atoms`, `vibrations_many_atoms`, `phonons_many_atoms` and `md_many_atoms` over
-    ASE-like objects, for a class that has `compute_many`, `relax_many`, `neb_many`, `vibrations_many`, `phonons_many` and `md_many`
-    (a class without the latter five inherits adapters that fail where they are called)"""
+    """`calculate_many`, `relax_many_atoms`, `neb_many_atoms`, `vibrations_many_atoms`, `phonons_many_atoms`, `elastic_many_atoms` and
+    `md_many_atoms` over ASE-like objects, for a class that has `compute_many`, `relax_many`, `neb_many`, `vibrations_many`,
+    `phonons_many`, `elastic_many` and `md_many` (a class without the latter six inherits adapters that fail where they are called)"""
 
     def calculate_many(self, atoms_list) -> List[Dict[str, Any]]:
         """`compute_many` over ASE-like objects (anything with get_atomic_numbers / get_positions / get_cell / get_pbc)"""
@@ -96,6 +96,11 @@ class ManyAtomsMixin:
         atoms_list = list(atoms_list)
         numbers, positions, cells, pbcs = atoms_args(atoms_list)
         return self.phonons_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, supercells, **kw)
+
+    def elastic_many_atoms(self, atoms_list, **kw) -> List[Dict[str, Any]]:
+        """`elastic_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc); nothing is written
+        back to them"""
+        return self.elastic_many(*atoms_args(atoms_list), **kw)
 
     def md_many_atoms(self, atoms_list, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:
         """`md_many` over ASE-like objects (get_atomic_numbers / get_positions / get_masses / get_cell / get_pbc, and

@@ -225,6 +225,7 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         self.neb_info: Optional[Dict[str, int]] = None     # counters of the last neb_many call
         self.vib_info: Optional[Dict[str, int]] = None     # counters of the last vibrations_many call
         self.phonon_info: Optional[Dict[str, int]] = None  # counters of the last phonons_many call
+        self.elastic_info: Optional[Dict[str, int]] = None  # counters of the last elastic_many call
         for z, t in self.type_map.items():
             self._z2type[z] = t
 
@@ -376,6 +377,29 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
                                                   symprec=symprec, want_modes=want_modes, dos_bins=dos_bins,
                                                   max_atoms_per_call=max_atoms_per_call,
                                                   want_atomic_virial=self.compute_atomic_virial, **kw)
+        return results
+
+    def elastic_many(self, numbers_list, positions_list, cells, pbcs, *, delta: float = 0.005, nfree: int = 2,
+                     relax_ions: bool = False, ion_delta: float = 0.01, max_atoms_per_call: int = 32768, **kw) -> List[Dict[str, Any]]:
+        """Second-order elastic tensors of B crystals at once (sevennet_amd.elastic.elastic_batch): central differences of the
+        stress over 6 nfree homogeneously strained copies per system (strain step delta, a shear step being the engineering
+        strain; nfree 2 or 4), written, evaluated in batches of at most max_atoms_per_call atoms and reduced on the GPU.  Every
+        system must be periodic along all three axes.  relax_ions: also let the ions follow the strain, through the Gamma
+        Hessian (vibrations_many's kernels, displacement ion_delta in A) and the internal-strain tensor.  Further kw: extra /
+        make_extra (as elastic_batch).  One dict per system, in the given order: the keys of `compute` for the unstrained
+        structure plus `stress_strain` [6,6] (raw d sigma_i / d epsilon_j, eV/A^3, Voigt order xx, yy, zz, yz, xz, xy),
+        `elastic_tensor` [6,6] (its symmetric part: the elastic tensor where the unstrained `stress` is about zero),
+        `asymmetry`, `internal_strain` [n,3,6], `fmax`, `compliance`, `bulk_modulus` / `shear_modulus` (`voigt`, `reuss`, `hill`),
+        `youngs_modulus`, `poisson_ratio`, `stable` and `status` ('ok', 'failed' or 'singular'); with relax_ions `elastic_tensor`
+        is the relaxed-ion one, beside `elastic_tensor_clamped`, `hessian` and `ion_eigenvalues`.  elastic.GPA converts to GPa.
+        The call's counters are kept as `self.elastic_info`."""
+        from .elastic import elastic_batch
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        results, self.elastic_info = elastic_batch(self.model, self._types_list(numbers_list), list(positions_list), cells, pbcs,
+                                                   cutoff=self.cutoff, delta=delta, nfree=nfree, relax_ions=relax_ions,
+                                                   ion_delta=ion_delta, max_atoms_per_call=max_atoms_per_call,
+                                                   want_atomic_virial=self.compute_atomic_virial, **kw)
         return results
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, **kw) -> List[Dict[str, Any]]:

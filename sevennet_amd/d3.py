@@ -353,6 +353,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         self.neb_info = None     # counters of the last neb_many call
         self.vib_info = None     # counters of the last vibrations_many call
         self.phonon_info = None  # counters of the last phonons_many call
+        self.elastic_info = None  # counters of the last elastic_many call
 
     @staticmethod
     def _sum(a, b) -> Dict[str, Any]:
@@ -496,6 +497,32 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         results = snet.phonons_many(numbers_list, positions_list, masses_list, cells, pbcs, supercells, make_extra=make_extra, **kw)
         self.phonon_info = snet.phonon_info
         at_base = d3.compute_many(built['numbers'], built['positions'], built['cells'], np.ones((len(numbers_list), 3), bool))
+        return [self._sum(a, b) for a, b in zip(results, at_base)]
+
+    def elastic_many(self, numbers_list, positions_list, cells, pbcs, d3_term: str = 'device', **kw) -> List[Dict[str, Any]]:
+        """`SevenNetCalculator.elastic_many` on the sum of the model's and the D3 stresses and forces (sevennet_amd.elastic): the
+        tensors are those of model + D3, the keys of `compute` for the unstrained structures are the summed ones.  The counters
+        are kept as `self.elastic_info`.  Only d3_term = 'device' is available: its `D3DeviceTerm`, built over the copy slots with
+        their strained cells (make_extra), carries the virial the stresses need; d3_term = 'host' raises ValueError, as under
+        relax_cell=True in `relax_many`."""
+        self._check_d3_term(d3_term)
+        if d3_term == 'host':
+            raise ValueError("elastic_many is not available with d3_term='host': that D3 term reaches the driver through the `extra` "
+                             "contract, which carries forces and energies but no virial, so its stress is unknown (pass "
+                             "d3_term='device', whose term carries one)")
+        snet, d3 = self.calcs
+        numbers_list, positions_list = list(numbers_list), [np.asarray(p, np.float64) for p in positions_list]
+        if len(numbers_list) != len(positions_list):
+            raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
+        pbcs_b = np.broadcast_to(np.asarray(pbcs, bool).reshape(-1, 3), (len(numbers_list), 3))
+
+        def make_extra(slot_system, slot_cells):   # the D3 term over the copy slots: slot s holds a copy of system slot_system[s] in slot_cells[s]
+            return self._d3_term([numbers_list[b] for b in slot_system], [positions_list[b] for b in slot_system], slot_cells,
+                                 pbcs_b[slot_system], d3_term)
+
+        results = snet.elastic_many(numbers_list, positions_list, cells, pbcs, make_extra=make_extra, **kw)
+        self.elastic_info = snet.elastic_info
+        at_base = d3.compute_many(numbers_list, positions_list, cells, pbcs)
         return [self._sum(a, b) for a, b in zip(results, at_base)]
 
     def md_many(self, numbers_list, positions_list, masses_list, cells, pbcs, dt: float, steps: int, d3_term: str = 'host',

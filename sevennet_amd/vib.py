@@ -86,7 +86,8 @@ def validate_vib_inputs(n_atoms, masses, indices, delta, nfree, max_atoms_per_ca
     return masses, selected
 
 
-def plan_copies(n_atoms, selected: Sequence[np.ndarray], nfree: int, max_atoms_per_call: int) -> SimpleNamespace:
+def plan_copies(n_atoms, selected: Optional[Sequence[np.ndarray]], nfree: int, max_atoms_per_call: int,
+                n_groups: Optional[Sequence[int]] = None) -> SimpleNamespace:
     """The copies of B systems packed into calls (a pure function of its arguments).  n_atoms [B]; selected[b]: the displaced
     atoms of system b (indices within the system).  System b has 3 m_b ROW GROUPS -- the nfree copies of one (atom a, axis i), in
     the order of STENCIL[nfree] -- and one undisplaced copy.  Row groups are never split; a call holds at most
@@ -102,11 +103,15 @@ def plan_copies(n_atoms, selected: Sequence[np.ndarray], nfree: int, max_atoms_p
     -> plan with `slot_system` int64 [S] (the system of each slot), `n_groups` [B] and `calls`: a list of namespaces with `ids`
     int64 [c] (the slots of the call's copies, ascending), `desc` int32 [c,4] (system, atom, axis, q per copy), `groups` int32
     [g,3] (first copy within the call, system, row r = 3 (position of a in selected[b]) + i) and `base` (pairs (copy within the
-    call, system) of the undisplaced copies)."""
+    call, system) of the undisplaced copies).
+
+    n_groups [B]: the number of row groups of each system where they are not the coordinates of selected atoms (the six strain
+    patterns of elastic.py).  `selected` is then not read, row r of system b is an index 0 .. n_groups[b] - 1 of the caller's, and
+    the descriptor of its copies is (system, r, 0, q)."""
     n = np.asarray(n_atoms, np.int64).reshape(-1)
     B = len(n)
     qs = STENCIL[nfree]
-    G = np.array([3 * len(s) for s in selected], np.int64)
+    G = np.array([3 * len(s) for s in selected], np.int64) if n_groups is None else np.array(n_groups, np.int64).reshape(-1)
     budget = int(max_atoms_per_call)
     g = np.ones(B, np.int64)
     lo, hi = 1, int(G.max())   # the smallest K whose slots fit (the slots' atom count does not grow with K)
@@ -136,7 +141,7 @@ def plan_copies(n_atoms, selected: Sequence[np.ndarray], nfree: int, max_atoms_p
                     groups.append((len(desc), b, r))
                     for w, q in enumerate(qs):
                         ids.append(slot0[b] + nfree * k + w)
-                        desc.append((b, int(selected[b][r // 3]), r % 3, q))
+                        desc.append((b, int(selected[b][r // 3]), r % 3, q) if n_groups is None else (b, r, 0, q))
                 if t > 0:
                     used += t * nfree * int(n[b])
                     n_items += t
