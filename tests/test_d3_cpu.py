@@ -46,6 +46,22 @@ def test_blob_holds_the_published_tables():
     assert z['damp_zero_params'][zn.index('b2-plyp')][0] == 0.64
     c = z['c6ab']
     assert (c[:, 0] > 0).all() and c[:, 1].max() < 600 and (c[:, 3:] >= 0).all()
+    # mxc[Z], the number of reference coordination numbers per element: 7 elements have one (He Ne Ar Kr Xe Ce Rn), 37 two, 33
+    # three, 11 four, 6 five
+    zi, ri, zj, rj = (c[:, 1].astype(int) % 100, c[:, 1].astype(int) // 100, c[:, 2].astype(int) % 100, c[:, 2].astype(int) // 100)
+    assert zi.min() == 1 and zi.max() == 94 and zj.min() == 1 and zj.max() == 94 and max(ri.max(), rj.max()) == 4
+    mxc = np.zeros(95, int)
+    np.maximum.at(mxc, zi, ri + 1)
+    np.maximum.at(mxc, zj, rj + 1)
+    assert np.bincount(mxc[1:], minlength=6).tolist() == [0, 7, 37, 33, 11, 6]
+    assert np.nonzero(mxc == 1)[0].tolist() == [2, 10, 18, 36, 54, 58, 86]
+    # no (a, b) inside an element pair's mxc_i x mxc_j box is missing: the `e[0] <= 0` skip of d3_c6 (csrc/snet_d3.hip; the
+    # reference's `c6ref > 0`) never fires on this blob -- it only guards against a damaged one
+    have = np.zeros((95, 95, 5, 5), bool)
+    have[zi, zj, ri, rj] = have[zj, zi, rj, ri] = True
+    a = np.arange(5)
+    box = (a[None, None, :, None] < mxc[:, None, None, None]) & (a[None, None, None, :] < mxc[None, :, None, None])
+    assert np.array_equal(have, box)
 
 
 def test_oracle_matches_reference_known_answers_periodic():
