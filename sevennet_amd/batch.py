@@ -31,6 +31,18 @@ def _as_host(x, dtype) -> np.ndarray:
     return np.asarray(x, dtype)
 
 
+def to_device(a, dtype, dev) -> torch.Tensor:
+    """a host array as a tensor of `dtype` on `dev`"""
+    return torch.as_tensor(np.ascontiguousarray(a)).to(dev, dtype)
+
+
+def device_positions(positions, dev) -> torch.Tensor:
+    """positions (a tensor anywhere, or a host array) as fp64 [N,3] on `dev`.  A tensor that is that already comes back itself:
+    who writes to the result clones it first."""
+    return (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
+            else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3)
+
+
 def _pad_cells(cells: np.ndarray, pbcs: np.ndarray, cutoff: float) -> np.ndarray:
     """cells[B,3,3] with the zero rows of open axes replaced by a lattice vector along that axis (dataload.py:37-48; the edge
     set does not depend on its length, see snet_batch.hip)"""
@@ -274,8 +286,7 @@ def build_batch_graph(types, positions, cells, pbcs, cutoff: float, num_species:
         raise ValueError(f'system {b}: cells on the device are read by the batched neighbor kernel only, which does not take this '
                          f'system ({"more than " + str(max_atoms) + " atoms" if kind[b] == 1 else "a periodic height below cutoff / 64"})')
     with torch.cuda.device(dev):
-        pos = positions.to(dev, torch.float64).contiguous() if isinstance(positions, torch.Tensor) \
-            else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)
+        pos = device_positions(positions, dev).contiguous()
         fast = np.nonzero(kind == 0)[0]
         if len(fast) == B:   # every system in the batched kernel: the graph IS its output
             row_ptr, src, center, ev, shifts, E = _batched_neighbors(pos, a_ptr, cells, pbcs, cutoff, dev, with_shifts, bad_types, cells_dev)

@@ -451,7 +451,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         """`SevenNetCalculator.vibrations_many` on the sum of the model's and the D3 forces (sevennet_amd.vib): the Hessians and
         spectra are those of model + D3, the keys of `compute` for the undisplaced structures are the summed ones.  The
         counters are kept as `self.vib_info`.  d3_term as in `relax_many`: 'host' prepares the D3 batch of each call's copies
-        on the host, 'device' keeps the term on the device, planned once per layout of the copy slots (vib.plan_copies)."""
+        on the host, 'device' keeps the term on the device, planned once per layout of the copy slots (fd.plan_copies)."""
         self._check_d3_term(d3_term)
         snet, d3 = self.calcs
         numbers_list, positions_list = list(numbers_list), [np.asarray(p, np.float64) for p in positions_list]

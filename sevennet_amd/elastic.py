@@ -6,7 +6,7 @@ patterns (Voigt j = 0 .. 5 in ASE order xx, yy, zz, yz, xz, xy; a shear step is 
 and one unstrained copy: 6 nfree + 1 evaluations.  `plan_elastic` gives every copy (b, j, q) a slot of its own -- the strained
 cells and volumes of the slots are computed once on the host, in fp64, by the expression the kernel applies to the positions, and
 are what the force call and a D3 term are built with -- and packs the copies into calls of at most `max_atoms_per_call` atoms with
-`vib.plan_copies`.  Per call one `snet_el_strain` launch writes the copies from the base positions (uploaded once), one batched
+`fd.plan_copies`.  Per call one `snet_el_strain` launch writes the copies from the base positions (uploaded once), one batched
 evaluation (sevennet_amd.batch) gives their virials and forces and one `snet_el_rows` launch writes the columns of the raw
 stress-strain matrix S = d sigma / d epsilon and the rows of the internal-strain tensor L = d F / d epsilon they determine.  Each is
 written by one workgroup of one call, so nothing is accumulated across calls and the result does not depend on the packing.
@@ -27,8 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import BatchForces, _as_host, validate_batch_inputs, virial_to_stress
-from .vib import STENCIL, plan_copies, vib_loop
+from .batch import BatchForces, _as_host, device_positions, to_device, validate_batch_inputs
+from .fd import STENCIL, BaseCopies, call_info, check_extra, check_refused, copy_calls, plan_copies, refused_count, write_copies
+from .vib import vib_loop
 
 GPA = 160.21766208   # GPa per eV/A^3
 ELASTIC_STATUS_NAMES = ('ok', 'failed', 'singular')
@@ -80,7 +81,7 @@ def strain_rows(x, j: int, q: int, delta: float) -> np.ndarray:
 
 
 def plan_elastic(n_atoms, cells, delta: float, nfree: int, max_atoms_per_call: int) -> SimpleNamespace:
-    """The strained copies of B systems packed into calls by `vib.plan_copies` with six row groups per system (a pure function
+    """The strained copies of B systems packed into calls by `fd.plan_copies` with six row groups per system (a pure function
     of its arguments).  Every copy has a slot of its own, because its cell is its own: slot (6 nfree + 1) b + nfree j + w holds
     copy (b, j, STENCIL[nfree][w]) and slot (6 nfree + 1) b + 6 nfree the unstrained copy.
     -> plan with `slot_system` int64 [S], `slot_desc` int32 [S,3] (system, j, q), `slot_cells` fp64 [S,3,3] (cell F),
@@ -109,18 +110,9 @@ def plan_elastic(n_atoms, cells, delta: float, nfree: int, max_atoms_per_call: i
 
 
 # ------------------------------------------------------------------------------------------------ launches
-def el_strain(pos0: torch.Tensor, seg_ptr0: torch.Tensor, desc: torch.Tensor, copy_ptr: torch.Tensor, delta: float,
-              pos_out: torch.Tensor, status: torch.Tensor) -> None:
-    """one `snet_el_strain` launch on the current stream (dtypes as the C ABI: pos0 / pos_out fp64, the rest int32)"""
-    n0, n_sys, n_copies, n_out = int(pos0.shape[0]), int(seg_ptr0.numel()) - 1, int(desc.shape[0]), int(pos_out.shape[0])
-    f64, i32 = torch.float64, torch.int32
-    _lib.check_device_tensors('el_strain', pos0, [(pos0, f64, (n0, 3)), (seg_ptr0, i32, (n_sys + 1,)), (desc, i32, (n_copies, 3)),
-                                                  (copy_ptr, i32, (n_copies + 1,)), (pos_out, f64, (n_out, 3)),
-                                                  (status, i32, (n_copies,))])
-    P = _lib.ptr
-    with torch.cuda.device(pos0.device):
-        _lib.check(_lib.load().snet_el_strain(P(pos0), n0, P(seg_ptr0), n_sys, P(desc), P(copy_ptr), n_copies, float(delta),
-                                              P(pos_out), n_out, P(status), _lib.stream()), 'snet_el_strain')
+def el_strain(pos0, seg_ptr0, desc, copy_ptr, delta, pos_out, status) -> None:
+    """one `snet_el_strain` launch on the current stream (fd.write_copies; desc int32 [c,3])"""
+    write_copies('snet_el_strain', 3, pos0, seg_ptr0, desc, copy_ptr, delta, pos_out, status)
 
 
 def el_rows(virial: torch.Tensor, virial_extra: Optional[torch.Tensor], volume: torch.Tensor, forces: torch.Tensor,
@@ -158,13 +150,13 @@ def el_finish(S: torch.Tensor, status: torch.Tensor, C: torch.Tensor, asymmetry:
 
 
 # ------------------------------------------------------------------------------------------------ the loop
-def elastic_loop(forces, plan, positions, n_atoms, *, on_call: Optional[Callable] = None, want_atomic_virial: bool = False):
+def elastic_loop(forces, plan, positions, n_atoms, *, keeper: Optional[Callable] = None, want_atomic_virial: bool = False):
     """The calls of a plan (`plan_elastic`).  forces: a BatchForces over the slots of `plan` (plan.slot_system, plan.slot_cells), or
     any object with its call interface (relax.fire_cell_loop documents it); the virial of its `extra`, if any, is read from
     `forces.virial_extra` after each call.  positions: the flat base positions [sum n_b, 3]; n_atoms [B].  Per call one
-    `snet_el_strain`, one force call and one `snet_el_rows`, nothing read back; on_call(call, graph, output, extra forces), if
-    given, is called after each force call (the driver keeps the unstrained copies' results with it; want_atomic_virial asks the
-    calls that hold such a copy for the per-atom virial).  Then one `snet_el_finish` and one transfer.
+    `snet_el_strain`, one force call (fd.copy_calls: keeper(call, graph, output, extra forces), if given, is called after each
+    force call -- the driver keeps the unstrained copies' results with it -- and want_atomic_virial asks the calls that hold such
+    a copy for the per-atom virial) and one `snet_el_rows`, nothing read back.  Then one `snet_el_finish` and one transfer.
     -> (S [B,6,6] raw d sigma_i / d epsilon_j in eV/A^3, L: per system [6,3 n_b] in eV/A, C [B,6,6], asymmetry [B], status [B] (0
     ok, 2 a non-finite virial or force or a volume that is not positive, 3 a layout the kernels refused), info)"""
     dev = forces.engine.dev
@@ -172,42 +164,25 @@ def elastic_loop(forces, plan, positions, n_atoms, *, on_call: Optional[Callable
     B, nfree, delta = len(n), plan.nfree, plan.delta
     a_ptr = np.concatenate([[0], np.cumsum(n)])
     f64, i32 = torch.float64, torch.int32
-
-    def up(a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a)).to(dev, dtype)
-
     with torch.cuda.device(dev):
-        pos0 = (positions.to(dev, f64) if isinstance(positions, torch.Tensor)
-                else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).contiguous()
-        seg0 = up(a_ptr, i32)
+        pos0 = device_positions(positions, dev).contiguous()
+        seg0 = to_device(a_ptr, i32, dev)
         S = torch.zeros(36 * B, dtype=f64, device=dev)
         L = torch.zeros(18 * int(a_ptr[-1]), dtype=f64, device=dev)
         status = torch.zeros(B, dtype=i32, device=dev)
         refused = []
-        for call in plan.calls:
-            copy_ptr = np.concatenate([[0], np.cumsum(n[call.desc[:, 0]])])
-            pos = torch.empty(int(copy_ptr[-1]), 3, dtype=f64, device=dev)
-            st = torch.zeros(len(call.ids), dtype=i32, device=dev)
-            el_strain(pos0, seg0, up(call.desc, i32), up(copy_ptr, i32), delta, pos, st)
-            refused.append(st)
-            g, out, fx, _ = forces(pos, call.ids, want_atomic_virial=want_atomic_virial and bool(call.base))
-            if on_call is not None:
-                on_call(call, g, out, fx)
+        for call, g, out, fx in copy_calls(forces, plan.calls, pos0, seg0, n, el_strain, delta, refused, want_atomic_virial, keeper):
             if len(call.groups):
-                el_rows(out['virial_per_system'], getattr(forces, 'virial_extra', None), up(plan.slot_volumes[call.ids], f64),
-                        out['forces'], fx, g.seg_ptr, up(call.groups, i32), nfree, delta, seg0, S, L, status)
+                el_rows(out['virial_per_system'], getattr(forces, 'virial_extra', None), to_device(plan.slot_volumes[call.ids], f64, dev),
+                        out['forces'], fx, g.seg_ptr, to_device(call.groups, i32, dev), nfree, delta, seg0, S, L, status)
         C, asym = torch.empty_like(S), torch.empty(B, dtype=f64, device=dev)
         el_finish(S, status, C, asym)
-        flat = torch.cat([S, C, asym, L, status.to(f64), torch.cat(refused).sum().to(f64).reshape(1)]).cpu().numpy()   # the one transfer
-    if flat[-1] != 0:
-        raise RuntimeError(f'snet_el_strain refused {int(flat[-1])} copies of the plan: its descriptors do not fit the systems')
+        flat = torch.cat([S, C, asym, L, status.to(f64), refused_count(refused)]).cpu().numpy()   # the one transfer
+    check_refused(flat[-1], el_strain)
     l0 = 73 * B
     L_h = [flat[l0 + 18 * a_ptr[b]:l0 + 18 * a_ptr[b + 1]].reshape(6, 3 * int(n[b])).copy() for b in range(B)]
-    n_rows_calls = sum(1 for c in plan.calls if len(c.groups))
-    info = dict(n_force_calls=forces.n_force_calls, copies_evaluated=int(sum(len(c.ids) for c in plan.calls)),
-                launches=len(plan.calls) + n_rows_calls + 1)
     return (flat[:36 * B].reshape(B, 6, 6).copy(), L_h, flat[36 * B:72 * B].reshape(B, 6, 6).copy(), flat[72 * B:73 * B].copy(),
-            flat[l0 + 18 * int(a_ptr[-1]):l0 + 18 * int(a_ptr[-1]) + B].astype(np.int64), info)
+            flat[l0 + 18 * int(a_ptr[-1]):l0 + 18 * int(a_ptr[-1]) + B].astype(np.int64), call_info(forces, plan.calls, 1))
 
 
 # ------------------------------------------------------------------------------------------------ host: relaxed ions, moduli
@@ -306,8 +281,7 @@ def elastic_batch(engine, types, positions, cells, pbcs, *, cutoff: float, delta
     input raises ValueError before any device work."""
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species, n_atoms)
     validate_elastic_inputs(n_at, cells, pbcs, delta, nfree, max_atoms_per_call, ion_delta)
-    if extra is not None and make_extra is not None:
-        raise ValueError('pass `extra` or `make_extra`, not both')
+    check_extra(extra, make_extra)
     if extra is not None and relax_ions:
         raise ValueError('relax_ions evaluates a second set of copies (the Hessian\'s): pass `make_extra`, which is called for each set')
     B = len(n_at)
@@ -319,27 +293,8 @@ def elastic_batch(engine, types, positions, cells, pbcs, *, cutoff: float, delta
         extra = make_extra(slot, plan.slot_cells)
     slot_types = lambda s: np.concatenate([types[a_ptr[b]:a_ptr[b + 1]] for b in s])   # noqa: E731
     forces = BatchForces(engine, slot_types(slot), n_at[slot], plan.slot_cells, pbcs[slot], cutoff, extra)
-    kept = []   # per call with unstrained copies: (systems, device tensors of their results)
-
-    def keep_base(call, g, out, fx):
-        if not call.base:
-            return
-        dev = out['forces'].device
-        sp = g.seg_ptr_host
-        copies = np.array([j for j, _ in call.base], np.int64)
-        rows = torch.as_tensor(np.concatenate([np.arange(sp[j], sp[j + 1]) for j in copies])).to(dev)
-        j_d = torch.as_tensor(copies).to(dev)
-        rp = g.row_ptr.long()
-        took = dict(energy=out['energy_per_system'][j_d].clone(), virial=out['virial_per_system'][j_d].clone(),
-                    forces=out['forces'][rows].clone(), energies=out['atomic_energy'][rows].clone(),
-                    n_edges=rp[torch.as_tensor(sp[copies + 1]).to(dev)] - rp[torch.as_tensor(sp[copies]).to(dev)])
-        if fx is not None:
-            took['forces_extra'] = fx[rows].clone()
-        if want_atomic_virial:
-            took['stresses'] = out['atomic_virial'][rows].clone()
-        kept.append(([b for _, b in call.base], took))
-
-    S, L, C, asym, status, info = elastic_loop(forces, plan, positions, n_at, on_call=keep_base, want_atomic_virial=want_atomic_virial)
+    base = BaseCopies(want_atomic_virial, keep_extra=True)
+    S, L, C, asym, status, info = elastic_loop(forces, plan, positions, n_at, keeper=base, want_atomic_virial=want_atomic_virial)
     hess = None
     if relax_ions:
         selected = [np.arange(int(k), dtype=np.int64) for k in n_at]
@@ -351,22 +306,10 @@ def elastic_batch(engine, types, positions, cells, pbcs, *, cutoff: float, delta
                                                    delta=ion_delta)
         hess = (H, h_asym, h_status)
         info = {k: info[k] + h_info[k] for k in info}
-    results: List[Optional[Dict[str, Any]]] = [None] * B
-    for systems, took in kept:
-        host = {k: v.cpu().numpy() for k, v in took.items()}
-        stress = virial_to_stress(host['virial'], cells[systems])
-        r0 = 0
-        for k, b in enumerate(systems):
-            r1 = r0 + int(n_at[b])
-            res = {'free_energy': float(host['energy'][k]), 'energy': float(host['energy'][k]),
-                   'energies': host['energies'][r0:r1].astype(np.float64), 'forces': host['forces'][r0:r1].astype(np.float64),
-                   'stress': stress[k], 'num_edges': int(host['n_edges'][k])}
-            if want_atomic_virial:
-                res['stresses'] = host['stresses'][r0:r1]
-            total = res['forces'] + host['forces_extra'][r0:r1] if 'forces_extra' in host else res['forces']
-            res['fmax'] = float(np.abs(total).max())
-            results[b] = res
-            r0 = r1
+    results = base.results(n_at, cells)
+    for res in results:   # (fmax: of the unstrained structure, the extra forces included)
+        fx = res.pop('forces_extra', None)
+        res['fmax'] = float(np.abs(res['forces'] if fx is None else res['forces'] + fx).max())
     volumes = np.abs(np.linalg.det(cells))
     for b in range(B):
         res = results[b]

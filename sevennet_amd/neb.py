@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import BatchForces, _pad_cells, batch_results, validate_batch_inputs
+from .batch import BatchForces, _pad_cells, batch_results, device_positions, to_device, validate_batch_inputs
 from .relax import RepackBook, check_fire_params, fire_step
 
 NEB_STATUS_NAMES = ('steps', 'converged', 'failed')   # 0: still running at the step cap; 2: the force kernel's guard switched the band off
@@ -168,16 +168,12 @@ def neb_loop(forces, n_images, positions, cells, pbcs, *, fmax: float, steps: in
     f64, i32 = torch.float64, torch.int32
     status_all, n_launches = np.zeros(B, np.int64), 0
 
-    def up(a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a)).to(dev, dtype)
-
     with torch.cuda.device(dev):
-        pos_all = (positions.to(dev, f64) if isinstance(positions, torch.Tensor)
-                   else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).clone()
+        pos_all = device_positions(positions, dev).clone()
         every = np.arange(B)
-        moving_rows = up(lay.rows(lay.interior_images(every)), torch.int64)
+        moving_rows = to_device(lay.rows(lay.interior_images(every)), torch.int64, dev)
         end_ids = lay.end_images(every)
-        pos_end = pos_all[up(lay.rows(end_ids), torch.int64)]
+        pos_end = pos_all[to_device(lay.rows(end_ids), torch.int64, dev)]
         _, out, fx, ex = forces(pos_end, end_ids)
         if fx is not None and ex is None:
             raise ValueError('neb: the extra term returned forces without energies, but the tangent of a band is chosen by the '
@@ -188,8 +184,9 @@ def neb_loop(forces, n_images, positions, cells, pbcs, *, fmax: float, steps: in
         vel = torch.zeros_like(pos)
         zero32 = torch.zeros(N, 3, dtype=torch.float32, device=dev)   # the `forces` of snet_fire_step: all of the force is f_neb
         f_neb = torch.zeros(N, 3, dtype=f64, device=dev)
-        fixed_d = None if fixed_h is None else up(fixed_h, i32)
-        k_d, cells_d, inv_d, pbc_d = up(k, f64).reshape(B), up(padded.reshape(B, 9), f64), up(inv.reshape(B, 9), f64), up(pbcs, i32)
+        fixed_d = None if fixed_h is None else to_device(fixed_h, i32, dev)
+        k_d, cells_d = to_device(k, f64, dev).reshape(B), to_device(padded.reshape(B, 9), f64, dev)
+        inv_d, pbc_d = to_device(inv.reshape(B, 9), f64, dev), to_device(pbcs, i32, dev)
         dt = torch.full((B,), float(params['dt_start']), dtype=f64, device=dev)
         alpha = torch.full((B,), float(params['alpha_start']), dtype=f64, device=dev)
         n_pos, n_steps, status, imax = (torch.zeros(B, dtype=i32, device=dev) for _ in range(4))
@@ -199,7 +196,8 @@ def neb_loop(forces, n_images, positions, cells, pbcs, *, fmax: float, steps: in
 
         def tables():   # of the bands in the batch: their moving images' ids, and the three offset arrays on the device
             ids = book.ids
-            return (lay.interior_images(ids), up(lay.ptr(ids, lay.m), i32), up(book.seg_ptr(), i32), up(lay.ptr(ids, 2 * lay.n), i32))
+            return (lay.interior_images(ids), to_device(lay.ptr(ids, lay.m), i32, dev), to_device(book.seg_ptr(), i32, dev),
+                    to_device(lay.ptr(ids, 2 * lay.n), i32, dev))
 
         def note(status_h, active_h, only_finished):
             for slot, b in enumerate(book.ids):
@@ -221,8 +219,8 @@ def neb_loop(forces, n_images, positions, cells, pbcs, *, fmax: float, steps: in
                 note(status_h, act_h, only_finished=True)
                 old_end = lay.ptr(book.ids, 2 * lay.n)
                 keep, rows = book.repack(pos, act_h, st_h)
-                rows_d, keep_d = up(rows, torch.int64), up(keep, torch.int64)
-                end_rows = up(np.concatenate([np.arange(old_end[s], old_end[s + 1]) for s in keep]), torch.int64)
+                rows_d, keep_d = to_device(rows, torch.int64, dev), to_device(keep, torch.int64, dev)
+                end_rows = to_device(np.concatenate([np.arange(old_end[s], old_end[s + 1]) for s in keep]), torch.int64, dev)
                 pos, vel, pos_end = pos[rows_d], vel[rows_d], pos_end[end_rows]   # (gathers copy: the stored slices keep the old buffer)
                 fixed_d = None if fixed_d is None else fixed_d[rows_d]
                 zero32, f_neb = zero32[:len(rows)], f_neb[:len(rows)]
@@ -351,24 +349,22 @@ def neb_batch(engine, types_list, images_list, cells, pbcs, *, cutoff: float, fm
     every = np.arange(B)
     f64, i32 = torch.float64, torch.int32
 
-    def up(a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a)).to(dev, dtype)
-
     with torch.cuda.device(dev):   # the NEB forces of the returned band: one launch on the evaluation above, every band active
         e_tot = out['energy_per_system'].to(f64) + (0.0 if ex is None else ex)
         inner, ends = lay.interior_images(every), lay.end_images(every)
-        rows = up(lay.rows(inner), torch.int64)
+        rows = to_device(lay.rows(inner), torch.int64, dev)
         padded, inv = mic_cells(cells, pbcs)
         fixed_h = _fixed_rows(lay, fixed)
         f_neb = torch.zeros(len(rows), 3, dtype=f64, device=dev)
         active, status_d, imax = torch.ones(B, dtype=i32, device=dev), torch.zeros(B, dtype=i32, device=dev), torch.zeros(B, dtype=i32, device=dev)
         band_ptr = lay.ptr(every, lay.m * lay.n)
-        neb_forces(final[rows], out['forces'][rows].contiguous(), e_tot[up(inner, torch.int64)].contiguous(),
-                   up(np.concatenate([[0], np.cumsum(n_at[inner])]), i32), up(lay.ptr(every, lay.m), i32),
-                   final[up(lay.rows(ends), torch.int64)], up(lay.ptr(every, 2 * lay.n), i32),
-                   e_tot[up(ends, torch.int64)].reshape(B, 2).contiguous(), up(padded.reshape(B, 9), f64), up(inv.reshape(B, 9), f64),
-                   up(pbcs, i32), up(k_arr, f64), active, status_d, f_neb, imax, climb=climb,
-                   forces_extra=None if fx is None else fx[rows].contiguous(), fixed=None if fixed_h is None else up(fixed_h, i32))
+        neb_forces(final[rows], out['forces'][rows].contiguous(), e_tot[to_device(inner, torch.int64, dev)].contiguous(),
+                   to_device(np.concatenate([[0], np.cumsum(n_at[inner])]), i32, dev), to_device(lay.ptr(every, lay.m), i32, dev),
+                   final[to_device(lay.rows(ends), torch.int64, dev)], to_device(lay.ptr(every, 2 * lay.n), i32, dev),
+                   e_tot[to_device(ends, torch.int64, dev)].reshape(B, 2).contiguous(), to_device(padded.reshape(B, 9), f64, dev),
+                   to_device(inv.reshape(B, 9), f64, dev), to_device(pbcs, i32, dev), to_device(k_arr, f64, dev), active, status_d, f_neb,
+                   imax, climb=climb, forces_extra=None if fx is None else fx[rows].contiguous(),
+                   fixed=None if fixed_h is None else to_device(fixed_h, i32, dev))
         norms = (f_neb * f_neb).sum(1).sqrt()
         neb_fmax = torch.stack([norms[int(band_ptr[b]):int(band_ptr[b + 1])].max() for b in range(B)]).cpu().numpy()
         imax_h, ok_h = imax.cpu().numpy(), status_d.cpu().numpy() == 0

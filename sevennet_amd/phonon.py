@@ -3,7 +3,7 @@ nearest-image rule and the dynamical matrices D(q) of many q-points, for many cr
 
 The rule is written out in include/snet_hip.h ("batched supercell phonons") and restated in fp64 numpy in tests/phonon_ref.py.
 System b is a primitive cell with m_b atoms and repeats (n1,n2,n3); `build_supercell` makes its N_b = m_b n1 n2 n3 atoms on the host,
-once, home cell first.  Only the m_b home atoms are displaced: `vib.plan_copies` packs the nfree 3 m_b displaced supercells and the
+once, home cell first.  Only the m_b home atoms are displaced: `fd.plan_copies` packs the nfree 3 m_b displaced supercells and the
 undisplaced one of every system into calls of at most `max_atoms_per_call` atoms, and per call `snet_vib_displace` writes the copies,
 one batched evaluation (sevennet_amd.batch) gives their forces and `snet_ph_rows` writes the rows of Phi [3 m_b, 3 N_b] they
 determine (written once each, so the result does not depend on the packing).  After the calls `snet_ph_finish` measures and, if
@@ -23,9 +23,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import BatchForces, _as_host, validate_batch_inputs, virial_to_stress
+from .batch import BatchForces, _as_host, device_positions, to_device, validate_batch_inputs
+from .fd import BaseCopies, call_info, check_extra, check_refused, copy_calls, plan_copies, refused_count
 from .md import ACC, KB
-from .vib import HBAR, INV_CM, VIB_STATUS_NAMES, plan_copies, validate_vib_inputs, vib_displace
+from .vib import HBAR, INV_CM, VIB_STATUS_NAMES, validate_vib_inputs, vib_displace
 
 REDUCED_SLACK = 1e-9   # |s_i|^2 <= |s_i + x s_j + y s_k|^2 (1 + this)
 
@@ -297,13 +298,13 @@ def ph_dynmat(phi: torch.Tensor, p_off: torch.Tensor, pos: torch.Tensor, sc_ptr:
 
 # ------------------------------------------------------------------------------------------------ the loop
 def phonon_loop(forces, plan, positions, n_super, n_home, masses, supercell_cells, q_cart: Sequence[np.ndarray], *, delta: float,
-                acoustic: bool = True, symprec: float = 1e-5, max_q_per_call: int = 4096, on_call: Optional[Callable] = None,
+                acoustic: bool = True, symprec: float = 1e-5, max_q_per_call: int = 4096, keeper: Optional[Callable] = None,
                 want_atomic_virial: bool = False):
     """The calls of a plan, then the sum rule, the images and D(q).  forces: a BatchForces over the copy slots of `plan` (made by
-    vib.plan_copies with n_atoms = n_super and the home atoms selected), or any object with its call interface; positions: the flat
+    fd.plan_copies with n_atoms = n_super and the home atoms selected), or any object with its call interface; positions: the flat
     supercell positions [sum N_b, 3], home cell first; n_super / n_home [B]; masses: per system, of the home atoms (amu);
     supercell_cells [B,3,3]; q_cart[b] [n_q_b, 3] in rad/A (n_q_b >= 1).  Per call one `snet_vib_displace`, one force call and one
-    `snet_ph_rows`, nothing read back; on_call as in vib.vib_loop.  Then one `snet_ph_finish`, one `snet_ph_images`, one
+    `snet_ph_rows`, nothing read back; keeper as in vib.vib_loop.  Then one `snet_ph_finish`, one `snet_ph_images`, one
     `snet_ph_dynmat` per at most `max_q_per_call` q-points (its R is dropped after each: the cap bounds that buffer, 144 m^2 bytes per
     q-point) and one transfer.
     -> (force constants: per system [m,N,3,3]; asr_defect [B]; D: per system complex [n_q,3m,3m]; hermiticity: per system [n_q];
@@ -318,37 +319,26 @@ def phonon_loop(forces, plan, positions, n_super, n_home, masses, supercell_cell
     q_start = np.concatenate([[0], np.cumsum(n_q)])
     q_sys = np.repeat(np.arange(B), n_q)
     S = np.asarray(supercell_cells, np.float64).reshape(B, 3, 3)
-
-    def up(a, dtype):
-        return torch.as_tensor(np.ascontiguousarray(a)).to(dev, dtype)
-
     with torch.cuda.device(dev):
-        pos0 = (positions.to(dev, f64) if isinstance(positions, torch.Tensor)
-                else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).contiguous()
-        sc_ptr, m_ptr = up(np.concatenate([[0], np.cumsum(N)]), i32), up(np.concatenate([[0], np.cumsum(m)]), i32)
-        off_d = up(p_off[:-1], i64)
+        pos0 = device_positions(positions, dev).contiguous()
+        sc_ptr, m_ptr = (to_device(np.concatenate([[0], np.cumsum(k)]), i32, dev) for k in (N, m))
+        off_d = to_device(p_off[:-1], i64, dev)
         phi = torch.zeros(int(p_off[-1]), dtype=f64, device=dev)
         status = torch.zeros(B, dtype=i32, device=dev)
         refused = []
-        for call in plan.calls:
-            copy_ptr = np.concatenate([[0], np.cumsum(N[call.desc[:, 0]])])
-            pos = torch.empty(int(copy_ptr[-1]), 3, dtype=f64, device=dev)
-            st = torch.zeros(len(call.ids), dtype=i32, device=dev)
-            vib_displace(pos0, sc_ptr, up(call.desc, i32), up(copy_ptr, i32), delta, pos, st)
-            refused.append(st)
-            g, out, fx, _ = forces(pos, call.ids, want_atomic_virial=want_atomic_virial and bool(call.base))
-            if on_call is not None:
-                on_call(call, g, out)
+        for call, g, out, fx in copy_calls(forces, plan.calls, pos0, sc_ptr, N, vib_displace, delta, refused, want_atomic_virial, keeper):
             if len(call.groups):
-                ph_rows(out['forces'], fx, g.seg_ptr, up(call.groups, i32), nfree, delta, m_ptr, sc_ptr, off_d, phi, status)
+                ph_rows(out['forces'], fx, g.seg_ptr, to_device(call.groups, i32, dev), nfree, delta, m_ptr, sc_ptr, off_d, phi, status)
         phi_out, asr = torch.empty_like(phi), torch.empty(B, dtype=f64, device=dev)
         ph_finish(phi, off_d, m_ptr, sc_ptr, acoustic, status, phi_out, asr)
-        S_d, Si_d, ioff_d = up(S.reshape(B, 9), f64), up(np.linalg.inv(S).reshape(B, 9), f64), up(i_off[:-1], i64)
+        S_d, Si_d = to_device(S.reshape(B, 9), f64, dev), to_device(np.linalg.inv(S).reshape(B, 9), f64, dev)
+        ioff_d = to_device(i_off[:-1], i64, dev)
         img_base = torch.empty(int(i_off[-1]), 3, dtype=i32, device=dev)
         img_mask = torch.empty(int(i_off[-1]), dtype=i32, device=dev)
-        ph_images(pos0, sc_ptr, m_ptr, up(np.repeat(np.arange(B), m), i32), S_d, Si_d, ioff_d, symprec, img_base, img_mask, status)
-        w_d = up(np.concatenate([1.0 / np.sqrt(np.asarray(ms, np.float64)) for ms in masses]), f64)
-        q_all = up(np.concatenate([np.asarray(q, np.float64).reshape(-1, 3) for q in q_cart]), f64)
+        ph_images(pos0, sc_ptr, m_ptr, to_device(np.repeat(np.arange(B), m), i32, dev), S_d, Si_d, ioff_d, symprec, img_base, img_mask,
+                  status)
+        w_d = to_device(np.concatenate([1.0 / np.sqrt(np.asarray(ms, np.float64)) for ms in masses]), f64, dev)
+        q_all = to_device(np.concatenate([np.asarray(q, np.float64).reshape(-1, 3) for q in q_cart]), f64, dev)
         D_parts, herm_parts, n_dyn = [], [], 0
         for g0 in range(0, int(q_start[-1]), int(max_q_per_call)):
             g1 = min(g0 + int(max_q_per_call), int(q_start[-1]))
@@ -357,13 +347,13 @@ def phonon_loop(forces, plan, positions, n_super, n_home, masses, supercell_cell
             R = torch.empty(int(d_off[-1]), 2, dtype=f64, device=dev)
             D, herm = torch.empty_like(R), torch.empty(g1 - g0, dtype=f64, device=dev)
             ph_dynmat(phi_out, off_d, pos0, sc_ptr, m_ptr, w_d, S_d, img_base, img_mask, ioff_d, q_all[g0:g1].contiguous(),
-                      up(q_sys[g0:g1], i32), up(q_ptr, i32), up(d_off[:-1], i64), int(m.max()), status, R, D, herm)
+                      to_device(q_sys[g0:g1], i32, dev), to_device(q_ptr, i32, dev), to_device(d_off[:-1], i64, dev), int(m.max()), status,
+                      R, D, herm)
             D_parts.append(D.reshape(-1))
             herm_parts.append(herm)
             n_dyn += 1
-        flat = torch.cat([phi_out, asr] + D_parts + herm_parts + [status.to(f64), torch.cat(refused).sum().to(f64).reshape(1)]).cpu().numpy()   # the one transfer
-    if flat[-1] != 0:
-        raise RuntimeError(f'snet_vib_displace refused {int(flat[-1])} copies of the plan: its descriptors do not fit the systems')
+        flat = torch.cat([phi_out, asr] + D_parts + herm_parts + [status.to(f64), refused_count(refused)]).cpu().numpy()   # the one transfer
+    check_refused(flat[-1], vib_displace)
     size, n_qt = int(p_off[-1]), int(q_start[-1])
     phi_h = [flat[p_off[b]:p_off[b + 1]].reshape(m[b], 3, N[b], 3).transpose(0, 2, 1, 3).copy() for b in range(B)]
     asr_h = flat[size:size + B].copy()
@@ -375,10 +365,7 @@ def phonon_loop(forces, plan, positions, n_super, n_home, masses, supercell_cell
     h0 = int(d_ptr[-1])
     herm_h = [flat[h0 + q_start[b]:h0 + q_start[b + 1]].copy() for b in range(B)]
     status_h = flat[h0 + n_qt:h0 + n_qt + B].astype(np.int64)
-    n_rows_calls = sum(1 for c in plan.calls if len(c.groups))
-    info = dict(n_force_calls=forces.n_force_calls, copies_evaluated=int(sum(len(c.ids) for c in plan.calls)),
-                launches=len(plan.calls) + n_rows_calls + 2 + n_dyn, q_evaluated=n_qt)
-    return phi_h, asr_h, D_h, herm_h, status_h, info
+    return phi_h, asr_h, D_h, herm_h, status_h, dict(call_info(forces, plan.calls, 2 + n_dyn), q_evaluated=n_qt)
 
 
 # ------------------------------------------------------------------------------------------------ the driver
@@ -411,8 +398,7 @@ def phonons_batch(engine, types, positions, masses, cells, pbcs, supercells, *, 
     masses, selected = validate_vib_inputs(n_at, masses, None, delta, nfree, max_atoms_per_call)
     repeats, q_list, mesh, temps = validate_phonon_inputs(n_at, cells, pbcs, supercells, qpoints, mesh, temperatures, symprec, e_min,
                                                           dos_bins, max_q_per_call)
-    if extra is not None and make_extra is not None:
-        raise ValueError('pass `extra` or `make_extra`, not both')
+    check_extra(extra, make_extra)
     B = len(n_at)
     a_ptr = np.concatenate([[0], np.cumsum(n_at)])
     positions = _as_host(positions, np.float64).reshape(-1, 3)
@@ -428,44 +414,14 @@ def phonons_batch(engine, types, positions, masses, cells, pbcs, supercells, *, 
     mesh_q = mesh_points(mesh) if mesh is not None else np.zeros((0, 3))
     q_frac = [np.concatenate([q_list[b], mesh_q]) for b in range(B)]
     q_cart = [2.0 * np.pi * (q_frac[b] @ np.linalg.inv(cells[b]).T) for b in range(B)]
-    kept = []   # per call with undisplaced copies: (systems, device tensors of their results)
-
-    def keep_base(call, g, out):
-        if not call.base:
-            return
-        dev = out['forces'].device
-        sp = g.seg_ptr_host
-        copies = np.array([j for j, _ in call.base], np.int64)
-        rows = torch.as_tensor(np.concatenate([np.arange(sp[j], sp[j + 1]) for j in copies])).to(dev)
-        j_d = torch.as_tensor(copies).to(dev)
-        rp = g.row_ptr.long()
-        took = dict(energy=out['energy_per_system'][j_d].clone(), virial=out['virial_per_system'][j_d].clone(),
-                    forces=out['forces'][rows].clone(), energies=out['atomic_energy'][rows].clone(),
-                    n_edges=rp[torch.as_tensor(sp[copies + 1]).to(dev)] - rp[torch.as_tensor(sp[copies]).to(dev)])
-        if want_atomic_virial:
-            took['stresses'] = out['atomic_virial'][rows].clone()
-        kept.append(([b for _, b in call.base], took))
-
+    base = BaseCopies(want_atomic_virial)
     phi, asr, D, herm, status, info = phonon_loop(forces, plan, np.concatenate([s[1] for s in sc]), N, n_at, masses, S, q_cart,
                                                   delta=delta, acoustic=acoustic, symprec=symprec, max_q_per_call=int(max_q_per_call),
-                                                  on_call=keep_base, want_atomic_virial=want_atomic_virial)
-    base: List[Optional[Dict[str, Any]]] = [None] * B
-    for systems, took in kept:
-        host = {k: v.cpu().numpy() for k, v in took.items()}
-        stress = virial_to_stress(host['virial'], S[systems])
-        r0 = 0
-        for k, b in enumerate(systems):
-            r1 = r0 + int(N[b])
-            res = {'free_energy': float(host['energy'][k]), 'energy': float(host['energy'][k]),
-                   'atomic_energies': host['energies'][r0:r1].astype(np.float64), 'forces': host['forces'][r0:r1].astype(np.float64),
-                   'stress': stress[k], 'num_edges': int(host['n_edges'][k])}
-            if want_atomic_virial:
-                res['stresses'] = host['stresses'][r0:r1]
-            base[b] = res
-            r0 = r1
+                                                  keeper=base, want_atomic_virial=want_atomic_virial)
+    base = base.results(N, S, 'atomic_energies')
     results = []
     for b in range(B):
-        res = dict(base[b])
+        res = base[b]
         n_path = len(q_list[b])
         res.update(supercell=repeats[b].copy(), supercell_positions=sc[b][1], supercell_cell=S[b].copy(), force_constants=phi[b],
                    asr_defect=float(asr[b]), qpoints=q_list[b].copy(), hermiticity=herm[b][:n_path].copy(),

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _MAX_IMAGE_REACH, BatchForces, batch_results, classify_systems, validate_batch_inputs
+from .batch import _MAX_IMAGE_REACH, BatchForces, batch_results, classify_systems, device_positions, validate_batch_inputs
 
 STATUS_NAMES = ('steps', 'converged', 'cell_failed')   # by the status word of snet_fire_cell_step (0: still running at the step cap)
 FIRE_DEFAULTS = dict(dt_start=0.1, dt_max=1.0, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, max_step=0.2)
@@ -164,8 +164,7 @@ def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack
     book = RepackBook(forces.n_atoms)
     B = book.B
     with torch.cuda.device(dev):
-        pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
-               else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).clone()
+        pos = device_positions(positions, dev).clone()
         vel = torch.zeros_like(pos)
         dt = torch.full((B,), float(params['dt_start']), dtype=torch.float64, device=dev)
         alpha = torch.full((B,), float(params['alpha_start']), dtype=torch.float64, device=dev)
@@ -238,8 +237,7 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
     book = RepackBook(forces.n_atoms)
     B = book.B
     with torch.cuda.device(dev):
-        pos = (positions.to(dev, torch.float64) if isinstance(positions, torch.Tensor)
-               else torch.as_tensor(np.ascontiguousarray(positions, np.float64)).to(dev)).reshape(-1, 3).clone()
+        pos = device_positions(positions, dev).clone()
         cell0 = torch.as_tensor(np.ascontiguousarray(np.asarray(cells, np.float64).reshape(B, 9))).to(dev)
         cell = cell0.clone()
         vel, vel_cell = torch.zeros_like(pos), torch.zeros_like(cell)
