@@ -60,10 +60,10 @@ def _flags() -> List[str]:
 
 
 def _stamp(src: str) -> str:
+    """hash of `src`, of every header it may include (all of csrc/*.h: a new header needs no entry here) and of the flags"""
     h = hashlib.sha1()
-    for p in [src, os.path.join(CSRC, 'snet_common.h'), os.path.join(CSRC, 'snet_split.h'), os.path.join(CSRC, 'snet_philox.h'),
-              os.path.join(INCLUDE, 'snet_hip.h'),
-              os.path.join(CSRC, 'generated', 'sh_generated.h')]:
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
+    for p in [src] + headers + [os.path.join(INCLUDE, 'snet_hip.h'), os.path.join(CSRC, 'generated', 'sh_generated.h')]:
         with open(p, 'rb') as f:
             h.update(f.read())
     h.update(' '.join(_flags()).encode())

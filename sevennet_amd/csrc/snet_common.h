@@ -1,4 +1,5 @@
-// Internal helpers shared by the gfx950 kernels of libsnet_hip.so.
+// Internal helpers shared by the gfx950 kernels of libsnet_hip.so: registries, macros, and the fp32 helpers of the model
+// kernels.  The helpers of the fp64 one-workgroup-per-system driver kernels are in snet_system.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -178,57 +179,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-// sums of NV per-thread values over a 256-thread workgroup, in a fixed order: xor tree inside a wave, then waves 0..3 in
-// sequence.  Every thread returns the same bits.  `sm` is reused by the next call: the trailing barrier protects it.
-// (the one-workgroup-per-system kernels: snet_relax.hip, snet_mdstep.hip)
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*sm)[4]) {
-#pragma unroll
-  for (int c = 0; c < NV; ++c) {
-    const double t = wave_sum_d(v[c]);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6][c] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < NV; ++c) v[c] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
-  __syncthreads();
-}
-// atoms [a0, a1) of system s of a batch of n atoms, clamped to [0, n] (the same kernels)
-struct Segment {
-  int64_t a0, a1;
-};
-__device__ __forceinline__ Segment segment(const int32_t *__restrict__ seg_ptr, int s, int64_t n) {
-  int64_t a0 = seg_ptr[s], a1 = seg_ptr[s + 1];
-  a0 = a0 < 0 ? 0 : (a0 > n ? n : a0);
-  a1 = a1 > n ? n : (a1 < a0 ? a0 : a1);
-  return Segment{a0, a1};
-}
-// force on atom i in fp64: the model's fp32 forces[3 i + k] widened, plus the fp64 forces_extra[3 i + k] when there is one
-__device__ __forceinline__ void load_force(const float *__restrict__ forces, const double *__restrict__ forces_extra, int64_t i,
-                                           double (&F)[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) F[k] = (double)forces[3 * i + k];
-  if (forces_extra) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) F[k] += forces_extra[3 * i + k];
-  }
-}
-// 3x3 matrices, row-major (the kernels that move a cell: snet_relax_cell.hip, snet_mdnpt.hip)
-__device__ __forceinline__ double det3(const double *a) {
-  return a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]);
-}
-// the smallest face-to-face height of the cell c: |det c| / |a_j x a_k| over the three axes
-__device__ __forceinline__ double min_height3(const double *c) {
-  const double vol = fabs(det3(c));
-  double h = INFINITY;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double *u = c + 3 * ((i + 1) % 3), *w = c + 3 * ((i + 2) % 3);
-    const double x = u[1] * w[2] - u[2] * w[1], y = u[2] * w[0] - u[0] * w[2], z = u[0] * w[1] - u[1] * w[0];
-    h = fmin(h, vol / sqrt(x * x + y * y + z * z));
-  }
-  return h;
 }
 
 // ---- cross-lane exchange at VALU speed (no LDS): gfx950 permlane swaps + DPP -------------------

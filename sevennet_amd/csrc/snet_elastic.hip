@@ -8,25 +8,13 @@
 // element of the copies, of S, L and C is computed by one thread in a written-out order, and the one reduction, the maximum of the
 // asymmetry, does not depend on its order.  No product is contracted with the sum that follows it, so the results equal the numpy
 // restatement of the same expressions bit for bit.
-#include "snet_common.h"
+#include "snet_system.h"
 
 namespace {
 
+using namespace snet;   // the shared device helpers (snet_system.h)
+
 constexpr int EL_THREADS = 256;
-constexpr int EL_WAVES = EL_THREADS / 64;
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for a NaN)
-
-// rows [a0, a1) of an array of n rows by ptr[s], ptr[s+1], or ok = false where they are not inside it (nothing is clamped: a
-// range that does not fit is refused)
-struct ElRange {
-  int64_t a0, a1;
-  bool ok;
-};
-__device__ __forceinline__ ElRange el_range(const int32_t *__restrict__ ptr, int s, int64_t n) {
-  const int64_t a0 = ptr[s], a1 = ptr[s + 1];
-  return ElRange{a0, a1, a0 >= 0 && a1 >= a0 && a1 <= n};
-}
 
 __global__ __launch_bounds__(EL_THREADS) void el_strain_kernel(
     const double *__restrict__ pos0, int64_t n0, const int32_t *__restrict__ seg_ptr0, int n_sys, const int32_t *__restrict__ desc,
@@ -35,20 +23,14 @@ __global__ __launch_bounds__(EL_THREADS) void el_strain_kernel(
   const int c = blockIdx.x;   // the copy
   const int tid = threadIdx.x;
   const int b = desc[3 * c], j = desc[3 * c + 1], q = desc[3 * c + 2];
-  bool ok = b >= 0 && b < n_sys && j >= 0 && j < 6 && q >= -2 && q <= 2;
-  const ElRange out = el_range(copy_ptr, c, n_out);
-  ok = ok && out.ok;
-  ElRange base{0, 0, false};
-  if (ok) {   // (seg_ptr0 is read only for a system that exists)
-    base = el_range(seg_ptr0, b, n0);
-    ok = base.ok && base.a1 - base.a0 == out.a1 - out.a0;
-  }
-  if (!ok) {   // refused before a row is read or written (uniform over the workgroup)
-    if (tid == 0) status[c] = 1;
+  const CopySlot slot = copy_slot(b, copy_ptr, c, n_out, seg_ptr0, n_sys, n0);
+  const Range base = slot.base, out = slot.out;
+  if (!(slot.ok && j >= 0 && j < 6 && q >= -2 && q <= 2)) {
+    if (tid == 0) status[c] = 1;   // refused before a row is read or written (uniform over the workgroup)
     return;
   }
   const int64_t na = base.a1 - base.a0;
-  const double s = (double)q * delta;   // rounded here, as snet_vib_displace rounds its shift
+  const double s = copy_step(q, delta);   // rounded here, as snet_vib_displace rounds its shift
   const double h = s * 0.5;             // (exact)
   // the axes of the pattern: j < 3 stretches axis j; yz, xz, xy shear the pair (a, bb)
   const int a = j < 3 ? j : (j == 3 ? 1 : 0), bb = j < 3 ? j : (j == 5 ? 1 : 2);
@@ -74,52 +56,44 @@ __global__ __launch_bounds__(EL_THREADS) void el_rows_kernel(
     int n_copies, const int32_t *__restrict__ group, int nfree, double delta, const int32_t *__restrict__ atom_ptr, int64_t n_base,
     int n_sys, double *__restrict__ S, double *__restrict__ L, int32_t *__restrict__ status) {
 #pragma clang fp contract(off)
-  const int g = blockIdx.x;   // the (system, column) group
   const int tid = threadIdx.x;
-  const int j0 = group[3 * g], b = group[3 * g + 1], j = group[3 * g + 2];
-  if (b < 0 || b >= n_sys) return;   // no system to report to: nothing is read or written
-  bool ok = j0 >= 0 && (int64_t)j0 + nfree <= n_copies && j >= 0 && j < 6;
-  const ElRange at = el_range(atom_ptr, b, n_base);
+  const RowGroup rg = row_group(group, blockIdx.x, nfree, n_copies, seg_ptr, n, n_sys);   // the (system, column) group
+  if (!rg.has_sys) return;   // no system to report to: nothing is read or written
+  const int j0 = rg.j0, b = rg.b, j = rg.r;
+  const Range at = checked_range(atom_ptr, b, n_base);
   const int64_t na = at.a1 - at.a0;
-  ok = ok && at.ok && na > 0;
-  int64_t a0[4] = {0, 0, 0, 0};
-  if (ok) {   // the copies of the group: inside the force arrays and of the system's size
-    for (int w = 0; w < nfree; ++w) {
-      const ElRange seg = el_range(seg_ptr, j0 + w, n);
-      ok = ok && seg.ok && seg.a1 - seg.a0 == na;
-      a0[w] = seg.a0;
-    }
-  }
-  if (!ok) {   // (uniform over the workgroup)
-    if (tid == 0) status[b] = 3;
+  if (!(rg.ok && j >= 0 && j < 6 && at.ok && na > 0 && rg.na == na)) {   // (the copies are of the system's size)
+    if (tid == 0) status[b] = 3;   // (uniform over the workgroup)
     return;
   }
+  // the copies come in the order q = -1, +1 (nfree 2) or q = -2, -1, +1, +2 (nfree 4); S and L are plain derivatives, which
+  // fd_stencil gives for the copies in the opposite order: copy w goes to place nfree - 1 - w
+  int64_t a0[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int w = 0; w < 4; ++w) a0[w] = nfree == 2 ? rg.a0[w ^ 1] : rg.a0[3 - w];   // (entries 2, 3 are not read with nfree 2)
   const double h2 = 2.0 * delta, h12 = 12.0 * delta;
   bool bad = false;
   if (tid < 6) {   // column j of S: sigma_i = -((virial + virial_extra)[perm i] / V') of each copy, then the stencil
     const int p = tid < 3 ? tid : (tid == 3 ? 4 : (tid == 4 ? 5 : 3));   // ASE Voigt (xx,yy,zz,yz,xz,xy) from the engine's (xx,yy,zz,xy,yz,zx)
     double sg[4];
-    for (int w = 0; w < nfree; ++w) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w >= nfree) break;
       const int64_t c = (int64_t)j0 + w;
       double t = virial[6 * c + p];
       if (virial_extra) t = t + virial_extra[6 * c + p];
       const double V = volume[c];
       if (!finite_d(t) || !finite_d(V) || !(V > 0.0)) bad = true;
-      sg[w] = -(t / V);
+      const double sigma = -(t / V);
+      if (nfree == 2) sg[w ^ 1] = sigma; else sg[3 - w] = sigma;
     }
-    // copies in the order q = -1, +1 (nfree 2) or q = -2, -1, +1, +2 (nfree 4)
-    S[36 * (int64_t)b + 6 * tid + j] = nfree == 2 ? (sg[1] - sg[0]) / h2 : (((8.0 * sg[2] - sg[3]) - 8.0 * sg[1]) + sg[0]) / h12;
+    S[36 * (int64_t)b + 6 * tid + j] = fd_stencil(sg, nfree, h2, h12);
   }
   double *__restrict__ row = L + 18 * at.a0 + (int64_t)j * 3 * na;
   for (int64_t c = tid; c < 3 * na; c += EL_THREADS) {
     double F[4];
-    for (int w = 0; w < nfree; ++w) {
-      const int64_t i = 3 * a0[w] + c;
-      F[w] = (double)forces[i];
-      if (forces_extra) F[w] = F[w] + forces_extra[i];
-      if (!finite_d(F[w])) bad = true;
-    }
-    row[c] = nfree == 2 ? (F[1] - F[0]) / h2 : (((8.0 * F[2] - F[3]) - 8.0 * F[1]) + F[0]) / h12;
+    if (!load_copy_forces(forces, forces_extra, a0, c, nfree, F)) bad = true;
+    row[c] = fd_stencil(F, nfree, h2, h12);
   }
   if (bad) status[b] = 2;   // (every writer of a system's status writes a non-zero value: any of them marks it failed)
 }
@@ -127,7 +101,7 @@ __global__ __launch_bounds__(EL_THREADS) void el_rows_kernel(
 __global__ __launch_bounds__(EL_THREADS) void el_finish_kernel(const double *__restrict__ S, const int32_t *__restrict__ status,
                                                                double *__restrict__ C, double *__restrict__ asym) {
 #pragma clang fp contract(off)
-  __shared__ double sm[EL_WAVES];
+  __shared__ double sm[4];
   const int b = blockIdx.x;   // the system
   const int tid = threadIdx.x;
   const double nan_d = __builtin_nan("");
@@ -139,11 +113,8 @@ __global__ __launch_bounds__(EL_THREADS) void el_finish_kernel(const double *__r
     C[36 * (int64_t)b + tid] = failed ? nan_d : (x + y) * 0.5;   // (x + y and y + x have the same bits: C[r,c] and C[c,r] do too)
     if (!failed) worst = fabs(x - y);
   }
-  // the maximum over the workgroup (exact in any order)
-  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
-  if ((tid & 63) == 0) sm[tid >> 6] = worst;
-  __syncthreads();
-  if (tid == 0) asym[b] = failed ? nan_d : fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+  worst = block_max(worst, sm);
+  if (tid == 0) asym[b] = failed ? nan_d : worst;
 }
 
 }  // namespace
@@ -151,13 +122,9 @@ __global__ __launch_bounds__(EL_THREADS) void el_finish_kernel(const double *__r
 extern "C" int snet_el_strain(const double *pos0, int64_t n0, const int32_t *seg_ptr0, int32_t n_sys, const int32_t *desc,
                               const int32_t *copy_ptr, int32_t n_copies, double delta, double *pos_out, int64_t n_out,
                               int32_t *status, void *stream) {
-  SNET_REQUIRE(n_sys >= 1 && n_copies >= 1 && n0 >= 0 && n0 < (1ll << 31) && n_out >= 0 && n_out < (1ll << 31),
-               "snet_el_strain: bad shape");
-  SNET_REQUIRE(pos0 && seg_ptr0 && desc && copy_ptr && pos_out && status && pos0 != pos_out, "snet_el_strain: null or aliased argument");
-  el_strain_kernel<<<(unsigned)n_copies, EL_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      pos0, n0, seg_ptr0, n_sys, desc, copy_ptr, delta, pos_out, n_out, status);
-  SNET_CHECK_LAUNCH("snet_el_strain");
-  return 0;
+  SNET_REQUIRE(!pos0 || pos0 != pos_out, "snet_el_strain: aliased argument");
+  return launch_copy_writer("snet_el_strain", el_strain_kernel, pos0, n0, seg_ptr0, n_sys, desc, copy_ptr, n_copies, delta, pos_out,
+                            n_out, status, stream);
 }
 
 extern "C" int snet_el_rows(const double *virial, const double *virial_extra, const double *volume, const float *forces,

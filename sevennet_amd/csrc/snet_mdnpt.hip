@@ -1,32 +1,18 @@
 // Batched isotropic NPT MD step: the BAOAB step of snet_mdstep.hip with the stochastic cell rescaling of Bernetti and Bussi,
 // J. Chem. Phys. 153, 114107 (2020), isotropic form, between the kicks and the drift.  One workgroup per system, fp64, every
-// per-system sum in the fixed order of snet::block_sum, no atomics and no value that crosses workgroups.  The rule is written
+// per-system sum in the fixed order of block_sum, no atomics and no value that crosses workgroups.  The rule is written
 // out in include/snet_hip.h (snet_mdb_npt_step) and restated in fp64 numpy in tests/md_npt_ref.py.
 //
 // The barostat is first order in the cell: one normal deviate per system and step (snet_philox.h, stream tag 2, atom word 0),
 // no barostat momentum.  Nothing of a system is written before its next cell has passed the guard.
-#include "snet_common.h"
-#include "snet_philox.h"
+#include "snet_system.h"
 
 namespace {
 
+using namespace snet;   // the shared device helpers (snet_system.h) and the noise stream (snet_philox.h)
+
 constexpr int NPT_THREADS = 256;
 constexpr int NPT_WAVES = NPT_THREADS / 64;
-constexpr double MD_ACC = 9.648533212e-3;   // eV / (A amu) in A / fs^2
-
-using snet::normals3;
-using snet::Segment;
-using snet::segment;
-using snet::STREAM_BAROSTAT;
-using snet::STREAM_THERMOSTAT;
-
-// a product that is never contracted with the sum that follows it: with mu == 1 the scaled position is the position, and the
-// drift after it rounds as in snet_mdb_step
-__device__ __forceinline__ double mul_rounded(double a, double b) {
-#pragma clang fp contract(off)
-  const double p = a * b;
-  return p;
-}
 
 struct NptParams {
   double dt, c1, c2, max_log_volume_step, min_height;
@@ -49,9 +35,7 @@ __global__ __launch_bounds__(NPT_THREADS) void mdb_npt_step_kernel(
   // thread reads the system's state before the first barrier, thread 0 writes it after the last)
   const int phase = active[s] == 1 ? p.phase : 0;
   const bool finish = (phase & 1) != 0, start = (phase & 2) != 0;
-  const double dt = p.dt, c1 = p.c1, c2 = p.c2;
-  const double half_kick = 0.5 * dt * MD_ACC;
-  const double kt = kT[s], kt_acc = kt * MD_ACC;
+  const double dt = p.dt, half_kick = 0.5 * dt * MD_ACC, kt = kT[s];
   const uint32_t sys = (uint32_t)sys_id[s], step = (uint32_t)step_index[s];
   double C[9];
 #pragma unroll
@@ -69,16 +53,13 @@ __global__ __launch_bounds__(NPT_THREADS) void mdb_npt_step_kernel(
     const double m = mass[i];
     double v[3] = {vel[3 * i + 0], vel[3 * i + 1], vel[3 * i + 2]};
     double F[3] = {0.0, 0.0, 0.0};
-    if (phase != 0) snet::load_force(forces, forces_extra, i, F);
-    if (finish) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;
-    }
+    if (phase != 0) load_force(forces, forces_extra, i, F);
+    if (finish) half_kick3(v, F, half_kick, m);
     mv2[0] += m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
   }
-  snet::block_sum<1>(mv2, sm);
+  block_sum<1>(mv2, sm);
   const double ek = 0.5 * mv2[0] / MD_ACC;
-  const double vol = fabs(snet::det3(C));
+  const double vol = fabs(det3(C));
   const double press = (2.0 * ek + trw) / (3.0 * vol);
   // the barostat step and the guard on the next cell
   double mu = 1.0;
@@ -94,13 +75,13 @@ __global__ __launch_bounds__(NPT_THREADS) void mdb_npt_step_kernel(
       de += amp * xi[0];
     }
     mu = exp(de / 3.0);
-    ok = (de - de == 0.0) && fabs(de) <= p.max_log_volume_step;   // (a NaN fails both)
+    ok = finite_d(de) && fabs(de) <= p.max_log_volume_step;   // (a NaN fails both)
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
       Cn[k] = mul_rounded(mu, C[k]);
-      ok = ok && (Cn[k] - Cn[k] == 0.0);
+      ok = ok && finite_d(Cn[k]);
     }
-    ok = ok && snet::min_height3(Cn) >= p.min_height;
+    ok = ok && min_height3(Cn) >= p.min_height;
   }
   if (tid == 0) {
     e_kin[s] = ek;
@@ -115,45 +96,10 @@ __global__ __launch_bounds__(NPT_THREADS) void mdb_npt_step_kernel(
     return;
   }
   if (phase == 0) return;
-  // pass 2: the kicks again (the same arithmetic on the same bits), the rescaling, the drift
-  for (int64_t i = seg.a0 + tid; i < seg.a1; i += NPT_THREADS) {
-    const double m = mass[i];
-    double v[3] = {vel[3 * i + 0], vel[3 * i + 1], vel[3 * i + 2]};
-    double F[3];
-    snet::load_force(forces, forces_extra, i, F);
-    if (finish) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;
-    }
-    if (start) {
-      double x[3] = {pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2]};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        x[k] = mul_rounded(mu, x[k]);
-        v[k] = v[k] / mu;
-      }
-      if (c2 == 0.0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[k] += dt * v[k];
-      } else {
-        double xi[3];
-        normals3(p.seed, (uint32_t)(i - seg.a0), sys, step, STREAM_THERMOSTAT, xi);
-        const double sigma = c2 * sqrt(kt_acc / m);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          x[k] += 0.5 * dt * v[k];
-          v[k] = c1 * v[k] + sigma * xi[k];
-          x[k] += 0.5 * dt * v[k];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) pos[3 * i + k] = x[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vel[3 * i + k] = v[k];
-  }
+  // pass 2: the atom step of snet_mdb_step (the kicks again: the same arithmetic on the same bits) with the rescaling by mu
+  const BaoabStep bs{finish, start, dt, p.c1, p.c2, half_kick, kt * MD_ACC, mu, p.seed, sys, step};
+  for (int64_t i = seg.a0 + tid; i < seg.a1; i += NPT_THREADS)
+    baoab_atom(bs, pos, vel, forces, forces_extra, mass, i, (uint32_t)(i - seg.a0));
   if (start && tid == 0) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) cell[9 * (int64_t)s + k] = Cn[k];

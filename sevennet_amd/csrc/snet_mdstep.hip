@@ -7,20 +7,14 @@
 // "Parallel random numbers: as easy as 1, 2, 3", SC11 (the Random123 constants), keyed by the seed and counted by (atom index
 // within its system, the caller's system id, the system's step, stream tag): what an atom draws does not depend on the batch
 // its system is in, on the slot it has there or on the launch grid.
-#include "snet_common.h"
-#include "snet_philox.h"
+#include "snet_system.h"
 
 namespace {
 
+using namespace snet;   // the shared device helpers (snet_system.h) and the noise stream (snet_philox.h)
+
 constexpr int MD_THREADS = 256;
 constexpr int MD_WAVES = MD_THREADS / 64;
-constexpr double MD_ACC = 9.648533212e-3;   // eV / (A amu) in A / fs^2
-
-using snet::normals3;   // the Philox4x32-10 / Box-Muller stream (snet_philox.h)
-using snet::STREAM_INIT;
-using snet::STREAM_THERMOSTAT;
-using snet::Segment;   // a system's clamped atom range (snet_common.h)
-using snet::segment;
 
 __global__ __launch_bounds__(MD_THREADS) void mdb_step_kernel(double *__restrict__ pos, double *__restrict__ vel,
                                                                const float *__restrict__ forces, const double *__restrict__ forces_extra,
@@ -33,51 +27,15 @@ __global__ __launch_bounds__(MD_THREADS) void mdb_step_kernel(double *__restrict
   const int s = blockIdx.x;
   const int tid = threadIdx.x;
   const Segment seg = segment(seg_ptr, s, n);
-  const bool finish = (phase & 1) != 0, start = (phase & 2) != 0;
-  const double half_kick = 0.5 * dt * MD_ACC;
-  const double kt_acc = kT[s] * MD_ACC;
-  const uint32_t sys = (uint32_t)sys_id[s], step = (uint32_t)step_index[s];   // (step_index is rewritten behind the barriers below)
+  const uint32_t step = (uint32_t)step_index[s];   // (step_index is rewritten behind the barriers below)
+  const BaoabStep p{(phase & 1) != 0, (phase & 2) != 0, dt, c1, c2, 0.5 * dt * MD_ACC, kT[s] * MD_ACC, 1.0, seed, (uint32_t)sys_id[s], step};
   double mv2[1] = {0.0};
-  for (int64_t i = seg.a0 + tid; i < seg.a1; i += MD_THREADS) {
-    const double m = mass[i];
-    double v[3] = {vel[3 * i + 0], vel[3 * i + 1], vel[3 * i + 2]};
-    double F[3] = {0.0, 0.0, 0.0};
-    if (phase != 0) snet::load_force(forces, forces_extra, i, F);
-    if (finish) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;
-    }
-    mv2[0] += m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (start) {
-      double x[3] = {pos[3 * i + 0], pos[3 * i + 1], pos[3 * i + 2]};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v[k] += half_kick * F[k] / m;
-      if (c2 == 0.0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) x[k] += dt * v[k];
-      } else {
-        double xi[3];
-        normals3(seed, (uint32_t)(i - seg.a0), sys, step, STREAM_THERMOSTAT, xi);
-        const double sigma = c2 * sqrt(kt_acc / m);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          x[k] += 0.5 * dt * v[k];
-          v[k] = c1 * v[k] + sigma * xi[k];
-          x[k] += 0.5 * dt * v[k];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) pos[3 * i + k] = x[k];
-    }
-    if (phase != 0) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) vel[3 * i + k] = v[k];
-    }
-  }
-  snet::block_sum<1>(mv2, sm);   // (its barriers: every thread has read step_index[s] before thread 0 writes it)
+  for (int64_t i = seg.a0 + tid; i < seg.a1; i += MD_THREADS)
+    mv2[0] += baoab_atom(p, pos, vel, forces, forces_extra, mass, i, (uint32_t)(i - seg.a0));
+  block_sum<1>(mv2, sm);   // (its barriers: every thread has read step_index[s] before thread 0 writes it)
   if (tid == 0) {
     e_kin[s] = 0.5 * mv2[0] / MD_ACC;
-    if (start) step_index[s] = (int32_t)(step + 1u);
+    if (p.start) step_index[s] = (int32_t)(step + 1u);
   }
 }
 

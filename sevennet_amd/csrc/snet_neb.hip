@@ -4,15 +4,14 @@
 // Phys. 113, 9901 (2000).  The rule is written out in include/snet_hip.h (snet_neb_forces).  The kernel turns the true forces and
 // the image energies of the interior images of many bands into NEB forces where they are; snet_fire_step (snet_relax.hip), called
 // with one segment per band, then moves all images of a band as the one system ASE's FIRE(NEB(images)) optimizes.
-#include "snet_common.h"
+#include "snet_system.h"
 
 namespace {
 
 constexpr int NEB_THREADS = 256;
 constexpr int NEB_WAVES = NEB_THREADS / 64;
 
-using snet::block_sum;    // per-image sums in a fixed order (snet_common.h)
-using snet::load_force;   // fp32 forces + optional fp64 forces_extra, in fp64
+using namespace snet;   // the shared device helpers (snet_system.h)
 
 struct NebCell {
   double c[9], inv[9];
@@ -24,16 +23,12 @@ struct NebCell {
 __device__ __forceinline__ void mic(const NebCell &q, double (&d)[3]) {
   if (!(q.px || q.py || q.pz)) return;
   double s[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) s[k] = d[0] * q.inv[k] + d[1] * q.inv[3 + k] + d[2] * q.inv[6 + k];
+  row_mul(d, q.inv, s);
   if (q.px) s[0] -= rint(s[0]);
   if (q.py) s[1] -= rint(s[1]);
   if (q.pz) s[2] -= rint(s[2]);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) d[j] = s[0] * q.c[j] + s[1] * q.c[3 + j] + s[2] * q.c[6 + j];
+  row_mul(s, q.c, d);
 }
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for a NaN)
 
 __global__ __launch_bounds__(NEB_THREADS) void neb_forces_kernel(
     const double *__restrict__ pos, const float *__restrict__ forces, const double *__restrict__ forces_extra,
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(NEB_THREADS) void neb_forces_kernel(
   }
   const int b = lo;
   const int j0 = img_ptr[b], j1 = img_ptr[b + 1];
-  const snet::Segment seg = snet::segment(seg_ptr, j, n);
+  const Segment seg = segment(seg_ptr, j, n);
   const int64_t a0 = seg.a0, a1 = seg.a1, na = a1 - a0;
   if (j < j0 || j >= j1 || j1 > n_img) return;   // an image no band owns: nothing of it is read or written
   const bool first = j == j0, last = j == j1 - 1;
@@ -63,14 +58,14 @@ __global__ __launch_bounds__(NEB_THREADS) void neb_forces_kernel(
   const double *prev = nullptr, *next = nullptr;
   bool layout_ok = e0 >= 0 && e0 + 2 * na <= n_end && (int64_t)end_ptr[b + 1] - e0 == 2 * na;
   if (!first) {
-    const snet::Segment sp = snet::segment(seg_ptr, j - 1, n);
+    const Segment sp = segment(seg_ptr, j - 1, n);
     layout_ok = layout_ok && sp.a1 - sp.a0 == na;
     prev = pos + 3 * sp.a0;
   } else {
     prev = pos_end + 3 * e0;
   }
   if (!last) {
-    const snet::Segment sn = snet::segment(seg_ptr, j + 1, n);
+    const Segment sn = segment(seg_ptr, j + 1, n);
     layout_ok = layout_ok && sn.a1 - sn.a0 == na;
     next = pos + 3 * sn.a0;
   } else {

@@ -7,18 +7,17 @@
 // atomics: every output element is written by one thread, every sum runs in a written-out order, and the two reductions over a
 // workgroup are maxima, which do not depend on their order.  No product is contracted with the sum that follows it.  A
 // descriptor that does not fit the buffers is refused with a status word: nothing is clamped, nothing out of range is touched.
-#include "snet_common.h"
+#include "snet_system.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // (this file's own text; the helpers of snet_system.h carry theirs)
 
 namespace {
 
+using namespace snet;   // the shared device helpers (snet_system.h)
+
 constexpr int PH_THREADS = 256;
-constexpr int PH_WAVES = PH_THREADS / 64;
 constexpr int PH_TILE = 1024;                // phases of one pass of ph_dynmat_rows_kernel: 2 x 8 KiB of LDS
 constexpr int64_t PH_MAX = 1ll << 31;
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for a NaN)
 
 // system b of a launch: its m home atoms are entries [h0, h0 + m) of the per-home-atom arrays and its N supercell atoms rows
 // [a0, a0 + N) of the per-atom arrays; ok = false where these do not lie inside [0, n_home] / [0, n_atoms], m < 1 or N is no
@@ -45,37 +44,20 @@ __device__ __forceinline__ void ph_image(const double *d0, const double *S, int 
   for (int c = 0; c < 3; ++c) d[c] = d0[c] + (((double)n1 * S[c] + (double)n2 * S[3 + c]) + (double)n3 * S[6 + c]);
 }
 
-__device__ __forceinline__ double ph_block_max(double x, double *sm, int tid) {
-  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
-  if ((tid & 63) == 0) sm[tid >> 6] = x;
-  __syncthreads();
-  return fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
-}
-
 // ------------------------------------------------------------------------------------------------ rows of Phi
 __global__ __launch_bounds__(PH_THREADS) void ph_rows_kernel(
     const float *__restrict__ forces, const double *__restrict__ forces_extra, int64_t n, const int32_t *__restrict__ seg_ptr,
     int n_copies, const int32_t *__restrict__ group, int nfree, double delta, const int32_t *__restrict__ m_ptr,
     const int32_t *__restrict__ sc_ptr, const int64_t *__restrict__ p_off, int n_sys, double *__restrict__ phi, int64_t p_size,
     int32_t *__restrict__ status) {
-  const int g = blockIdx.x;   // the row group
   const int tid = threadIdx.x;
-  const int j0 = group[3 * g], b = group[3 * g + 1], r = group[3 * g + 2];
-  if (b < 0 || b >= n_sys) return;   // no system to report to: nothing is read or written
-  bool ok = j0 >= 0 && (int64_t)j0 + nfree <= n_copies;
+  const RowGroup rg = row_group(group, blockIdx.x, nfree, n_copies, seg_ptr, n, n_sys);
+  if (!rg.has_sys) return;   // no system to report to: nothing is read or written
+  const int b = rg.b, r = rg.r;
   const PhSys s = ph_sys(m_ptr, sc_ptr, b, PH_MAX, PH_MAX);   // (m and N only: the forces are indexed through seg_ptr)
   const int64_t off = p_off[b];
-  ok = ok && s.ok && r >= 0 && r < 3 * s.m && ph_fits(off, p_size, 9, s.m, s.N);
-  int64_t a0[4] = {0, 0, 0, 0};
-  if (ok) {   // the copies of the group: inside the force arrays, each a whole supercell
-    for (int c = 0; c < nfree; ++c) {
-      const int64_t c0 = seg_ptr[j0 + c], c1 = seg_ptr[j0 + c + 1];
-      ok = ok && c0 >= 0 && c1 <= n && c1 - c0 == s.N;
-      a0[c] = c0;
-    }
-  }
-  if (!ok) {   // (uniform over the workgroup)
-    if (tid == 0) status[b] = 3;
+  if (!(rg.ok && s.ok && r >= 0 && r < 3 * s.m && ph_fits(off, p_size, 9, s.m, s.N) && rg.na == s.N)) {   // (each copy a whole supercell)
+    if (tid == 0) status[b] = 3;   // (uniform over the workgroup)
     return;
   }
   double *__restrict__ row = phi + off + (int64_t)r * 3 * s.N;
@@ -83,14 +65,8 @@ __global__ __launch_bounds__(PH_THREADS) void ph_rows_kernel(
   bool bad_force = false;
   for (int64_t c = tid; c < 3 * s.N; c += PH_THREADS) {
     double F[4];
-    for (int w = 0; w < nfree; ++w) {
-      const int64_t i = 3 * a0[w] + c;
-      F[w] = (double)forces[i];
-      if (forces_extra) F[w] = F[w] + forces_extra[i];
-      if (!finite_d(F[w])) bad_force = true;
-    }
-    // copies in the order q = -1, +1 (nfree 2) or q = -2, -1, +1, +2 (nfree 4): the stencil of snet_vib_rows
-    row[c] = nfree == 2 ? (F[0] - F[1]) / h2 : (((8.0 * F[1] - F[0]) - 8.0 * F[2]) + F[3]) / h12;
+    if (!load_copy_forces(forces, forces_extra, rg.a0, c, nfree, F)) bad_force = true;
+    row[c] = fd_stencil(F, nfree, h2, h12);   // the stencil of snet_vib_rows
   }
   if (bad_force) status[b] = 2;   // (every writer of a system's status writes a non-zero value: any of them marks it failed)
 }
@@ -100,7 +76,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_finish_kernel(
     const double *__restrict__ phi, const int64_t *__restrict__ p_off, const int32_t *__restrict__ m_ptr,
     const int32_t *__restrict__ sc_ptr, int64_t p_size, int acoustic, int32_t *__restrict__ status, double *__restrict__ phi_out,
     double *__restrict__ asr) {
-  __shared__ double sm[PH_WAVES];
+  __shared__ double sm[4];
   const int b = blockIdx.x;   // the system
   const int tid = threadIdx.x;
   const PhSys s = ph_sys(m_ptr, sc_ptr, b, PH_MAX, PH_MAX);
@@ -134,7 +110,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_finish_kernel(
     worst = fmax(worst, fabs(all));
     phi_out[off + r * n3 + 3 * a + k] = acoustic ? -others : row[3 * a + k];
   }
-  worst = ph_block_max(worst, sm, tid);
+  worst = block_max(worst, sm);
   if (tid == 0) asr[b] = worst;
 }
 
@@ -290,7 +266,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_dynmat_sym_kernel(
     const int32_t *__restrict__ m_ptr, int64_t n_home, const int64_t *__restrict__ i_off, int64_t i_size,
     const int32_t *__restrict__ q_sys, const int32_t *__restrict__ q_ptr, int n_q, const int64_t *__restrict__ d_off, int n_sys,
     const double *__restrict__ R, double *__restrict__ D, int64_t d_size, double *__restrict__ herm) {
-  __shared__ double sm[PH_WAVES];
+  __shared__ double sm[4];
   const int gq = blockIdx.x, tid = threadIdx.x;
   const int b = q_sys[gq];
   if (b < 0 || b >= n_sys) return;
@@ -309,9 +285,9 @@ __global__ __launch_bounds__(PH_THREADS) void ph_dynmat_sym_kernel(
     if (finite_d(diff)) worst = fmax(worst, diff);
     else not_finite = 1.0;
   }
-  worst = ph_block_max(worst, sm, tid);
+  worst = block_max(worst, sm);
   __syncthreads();
-  not_finite = ph_block_max(not_finite, sm, tid);
+  not_finite = block_max(not_finite, sm);
   if (tid == 0) herm[gq] = not_finite != 0.0 ? __builtin_nan("") : worst;
 }
 

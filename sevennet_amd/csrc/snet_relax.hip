@@ -3,7 +3,7 @@
 // FIRE: Bitzek, Koskinen, Gaehler, Moseler, Gumbsch, Phys. Rev. Lett. 97, 170201 (2006), in the form of ASE's optimizer (the
 // step is dt * v after the velocity update, clipped to max_step over the whole system).  Positions, velocities and the
 // per-system state (dt, alpha, n_pos, active, n_steps) stay on the device between steps; the host reads back n_active only.
-#include "snet_common.h"
+#include "snet_system.h"
 
 namespace {
 
@@ -15,20 +15,7 @@ constexpr int FIRE_WAVES = FIRE_THREADS / 64;
 // order (as the scratch of the two-stage reductions, they must not overlap on two streams).
 __device__ unsigned long long g_fire_arrivals = 0ull;
 
-struct FireParams {
-  double fmax, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
-  int n_min;
-};
-
-// max that keeps a NaN (a NaN force must not pass for a converged system)
-__device__ __forceinline__ double max_nan(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ double wave_max_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-using snet::block_sum;    // per-system sums in a fixed order (snet_common.h)
-using snet::load_force;   // fp32 forces + optional fp64 forces_extra, in fp64
+using namespace snet;   // the shared device helpers (snet_system.h)
 
 __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restrict__ pos, double *__restrict__ vel,
                                                                  const float *__restrict__ forces, const double *__restrict__ forces_extra,
@@ -43,7 +30,7 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
   const int tid = threadIdx.x;
   bool still_active = false;
   if (active_s[s] == 1) {   // (uniform over the workgroup)
-    const snet::Segment seg = snet::segment(seg_ptr, s, n);
+    const Segment seg = segment(seg_ptr, s, n);
     const int64_t a0 = seg.a0, a1 = seg.a1;
     // pass 1: max |F_i|^2, F.v, |F|^2, |v|^2
     double f2max = 0.0;
@@ -58,14 +45,10 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
       acc[1] += f2;
       acc[2] += vx * vx + vy * vy + vz * vz;
     }
-    {
-      const double t = wave_max_d(f2max);
-      if ((tid & 63) == 0) sm[tid >> 6][3] = t;
-    }
+    block_max_nan_put(f2max, sm);
     block_sum<3>(acc, sm);   // (its first barrier also publishes the four maxima; its second lets thread 0 go on alone)
     if (tid == 0) {
-      // sm[.][3] is not rewritten before the barrier below
-      const double fm = sqrt(max_nan(max_nan(sm[0][3], sm[1][3]), max_nan(sm[2][3], sm[3][3])));
+      const double fm = sqrt(block_max_nan_get(sm));   // (sm[.][3] is not rewritten before the barrier below)
       fmax_sys[s] = fm;
       if (fm < p.fmax) {
         active_s[s] = 0;
@@ -73,27 +56,13 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
       } else {
         double dt = dt_s[s], alpha = alpha_s[s];
         int n_pos = n_pos_s[s];
-        double keep, push;
-        if (acc[0] > 0.0) {
-          keep = 1.0 - alpha;
-          push = alpha;   // v <- keep v + ((push F) / |F|) |v|
-          if (n_pos > p.n_min) {
-            dt = fmin(dt * p.f_inc, p.dt_max);
-            alpha_s[s] = alpha * p.f_alpha;
-          }
-          n_pos += 1;
-        } else {
-          keep = 0.0;
-          push = 0.0;
-          alpha_s[s] = p.alpha_start;
-          dt = dt * p.f_dec;
-          n_pos = 0;
-        }
+        const FireMix mix = fire_decide(acc[0], p, dt, alpha, n_pos);
         dt_s[s] = dt;
+        alpha_s[s] = alpha;
         n_pos_s[s] = n_pos;
         n_steps_s[s] += 1;
-        sc[0] = keep;
-        sc[1] = push;
+        sc[0] = mix.keep;
+        sc[1] = mix.push;
         sc[2] = dt;
         sc[3] = 1.0;
       }
@@ -110,9 +79,7 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
         load_force(forces, forces_extra, i, F);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          double v = 0.0;
-          if (push > 0.0 || keep > 0.0) v = keep * vel[3 * i + k] + push * F[k] / nF * nV;
-          v = v + dt * F[k];
+          const double v = new_velocity(vel[3 * i + k], F[k], keep, push, nF, nV, dt);
           vel[3 * i + k] = v;
           const double dr = dt * v;
           d2[0] += dr * dr;
@@ -133,13 +100,7 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_step_kernel(double *__restr
       }
     }
   }
-  if (tid == 0) {   // count the active systems: one integer atomic per workgroup, the last arrival publishes the sum
-    const unsigned long long old = atomicAdd(&g_fire_arrivals, (1ull << 32) | (still_active ? 1ull : 0ull));
-    if ((unsigned)(old >> 32) == (unsigned)(n_sys - 1)) {
-      *n_active = (int32_t)((unsigned)(old & 0xffffffffull) + (still_active ? 1u : 0u));
-      atomicExch(&g_fire_arrivals, 0ull);
-    }
-  }
+  if (tid == 0) count_active(&g_fire_arrivals, still_active, n_sys, n_active);
 }
 
 }  // namespace
@@ -152,12 +113,8 @@ extern "C" int snet_fire_step(double *pos, double *vel, const float *forces, con
   SNET_REQUIRE(n_sys >= 1 && n_atoms >= 0 && n_atoms < (1ll << 31), "snet_fire_step: bad shape");
   SNET_REQUIRE(pos && vel && forces && seg_ptr && dt && alpha && n_pos && active && n_steps && fmax_sys && n_active,
                "snet_fire_step: null argument");
-  SNET_REQUIRE(fmax >= 0 && dt_start > 0 && dt_max >= dt_start && n_min >= 0 && f_inc >= 1 && f_dec > 0 && f_dec < 1 &&
-                   alpha_start > 0 && alpha_start <= 1 && f_alpha > 0 && f_alpha <= 1 && max_step > 0,
-               "snet_fire_step: FIRE parameters out of range");
-  FireParams p;
-  p.fmax = fmax, p.dt_max = dt_max, p.f_inc = f_inc, p.f_dec = f_dec, p.alpha_start = alpha_start, p.f_alpha = f_alpha;
-  p.max_step = max_step, p.n_min = n_min;
+  const FireParams p{fmax, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step, n_min};
+  SNET_REQUIRE(fire_params_ok(fmax, dt_start, p), "snet_fire_step: FIRE parameters out of range");
   fire_step_kernel<<<(unsigned)n_sys, FIRE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
       pos, vel, forces, forces_extra, n_atoms, seg_ptr, n_sys, dt, alpha, n_pos, active, n_steps, fmax_sys, n_active, p);
   SNET_CHECK_LAUNCH("snet_fire_step");

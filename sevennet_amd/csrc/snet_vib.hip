@@ -7,25 +7,13 @@
 // element of D, H and Hm is computed by one thread from at most four forces in a written-out order, and the one reduction, the
 // maximum of the asymmetry, does not depend on its order.  No product is contracted with the sum that follows it, so the
 // results equal the numpy restatement of the same expressions bit for bit.
-#include "snet_common.h"
+#include "snet_system.h"
 
 namespace {
 
+using namespace snet;   // the shared device helpers (snet_system.h)
+
 constexpr int VIB_THREADS = 256;
-constexpr int VIB_WAVES = VIB_THREADS / 64;
-
-__device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for a NaN)
-
-// rows [a0, a1) of a [n,3] array by seg_ptr[s], seg_ptr[s+1], or ok = false where they are not inside it (nothing is clamped:
-// a range that does not fit is refused)
-struct VibRange {
-  int64_t a0, a1;
-  bool ok;
-};
-__device__ __forceinline__ VibRange vib_range(const int32_t *__restrict__ ptr, int s, int64_t n) {
-  const int64_t a0 = ptr[s], a1 = ptr[s + 1];
-  return VibRange{a0, a1, a0 >= 0 && a1 >= a0 && a1 <= n};
-}
 
 __global__ __launch_bounds__(VIB_THREADS) void vib_displace_kernel(
     const double *__restrict__ pos0, int64_t n0, const int32_t *__restrict__ seg_ptr0, int n_sys, const int32_t *__restrict__ desc,
@@ -34,20 +22,14 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_displace_kernel(
   const int j = blockIdx.x;   // the copy
   const int tid = threadIdx.x;
   const int b = desc[4 * j], atom = desc[4 * j + 1], axis = desc[4 * j + 2], q = desc[4 * j + 3];
-  bool ok = b >= 0 && b < n_sys && axis >= 0 && axis < 3 && q >= -2 && q <= 2;
-  const VibRange out = vib_range(copy_ptr, j, n_out);
-  ok = ok && out.ok;
-  VibRange base{0, 0, false};
-  if (ok) {   // (seg_ptr0 is read only for a system that exists)
-    base = vib_range(seg_ptr0, b, n0);
-    ok = base.ok && base.a1 - base.a0 == out.a1 - out.a0 && atom >= 0 && atom < base.a1 - base.a0;
-  }
-  if (!ok) {   // refused before a row is read or written (uniform over the workgroup)
-    if (tid == 0) status[j] = 1;
+  const CopySlot slot = copy_slot(b, copy_ptr, j, n_out, seg_ptr0, n_sys, n0);
+  const Range base = slot.base, out = slot.out;
+  if (!(slot.ok && axis >= 0 && axis < 3 && q >= -2 && q <= 2 && atom >= 0 && atom < base.a1 - base.a0)) {
+    if (tid == 0) status[j] = 1;   // refused before a row is read or written (uniform over the workgroup)
     return;
   }
   const int64_t na = base.a1 - base.a0;
-  const double shift = (double)q * delta;   // rounded here, then added: x + q delta as numpy forms it
+  const double shift = copy_step(q, delta);   // rounded, then added: x + q delta as numpy forms it
   for (int64_t i = tid; i < 3 * na; i += VIB_THREADS) {
     const double x = pos0[3 * base.a0 + i];
     pos_out[3 * out.a0 + i] = (q != 0 && i == 3 * (int64_t)atom + axis) ? x + shift : x;
@@ -60,25 +42,15 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_rows_kernel(
     const int32_t *__restrict__ sel_ptr, int64_t n_sel, const int64_t *__restrict__ d_off, int n_sys, double *__restrict__ D,
     int64_t d_size, int32_t *__restrict__ status) {
 #pragma clang fp contract(off)
-  const int g = blockIdx.x;   // the row group
   const int tid = threadIdx.x;
-  const int j0 = group[3 * g], b = group[3 * g + 1], r = group[3 * g + 2];
-  if (b < 0 || b >= n_sys) return;   // no system to report to: nothing is read or written
-  bool ok = j0 >= 0 && (int64_t)j0 + nfree <= n_copies;
-  const VibRange s = vib_range(sel_ptr, b, n_sel);
+  const RowGroup rg = row_group(group, blockIdx.x, nfree, n_copies, seg_ptr, n, n_sys);
+  if (!rg.has_sys) return;   // no system to report to: nothing is read or written
+  const int b = rg.b, r = rg.r;
+  const int64_t na = rg.na;
+  const Range s = checked_range(sel_ptr, b, n_sel);
   const int64_t m3 = 3 * (s.a1 - s.a0), off = d_off[b];
-  ok = ok && s.ok && m3 > 0 && r >= 0 && r < m3 && off >= 0 && off <= d_size && m3 * m3 <= d_size - off;
-  int64_t a0[4] = {0, 0, 0, 0}, na = 0;
-  if (ok) {   // the copies of the group: inside the force arrays and all of one size
-    for (int c = 0; c < nfree; ++c) {
-      const VibRange seg = vib_range(seg_ptr, j0 + c, n);
-      ok = ok && seg.ok && (c == 0 || seg.a1 - seg.a0 == na);
-      a0[c] = seg.a0;
-      if (c == 0) na = seg.a1 - seg.a0;
-    }
-  }
-  if (!ok) {   // (uniform over the workgroup)
-    if (tid == 0) status[b] = 3;
+  if (!(rg.ok && s.ok && m3 > 0 && r >= 0 && r < m3 && off >= 0 && off <= d_size && m3 * m3 <= d_size - off)) {
+    if (tid == 0) status[b] = 3;   // (uniform over the workgroup)
     return;
   }
   double *__restrict__ row = D + off + (int64_t)r * m3;
@@ -90,16 +62,9 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_rows_kernel(
       bad_atom = true;
       continue;
     }
-    const int k = (int)(c % 3);
     double F[4];
-    for (int w = 0; w < nfree; ++w) {
-      const int64_t i = 3 * (a0[w] + atom) + k;
-      F[w] = (double)forces[i];
-      if (forces_extra) F[w] = F[w] + forces_extra[i];
-      if (!finite_d(F[w])) bad_force = true;
-    }
-    // copies in the order q = -1, +1 (nfree 2) or q = -2, -1, +1, +2 (nfree 4)
-    row[c] = nfree == 2 ? (F[0] - F[1]) / h2 : (((8.0 * F[1] - F[0]) - 8.0 * F[2]) + F[3]) / h12;
+    if (!load_copy_forces(forces, forces_extra, rg.a0, 3 * atom + c % 3, nfree, F)) bad_force = true;
+    row[c] = fd_stencil(F, nfree, h2, h12);
   }
   if (bad_atom) status[b] = 3;          // (every writer of a system's status writes a non-zero value: any of them marks it failed)
   else if (bad_force) status[b] = 2;
@@ -110,10 +75,10 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_finish_kernel(
     const double *__restrict__ w, int64_t d_size, int32_t *__restrict__ status, double *__restrict__ H,
     double *__restrict__ Hm, double *__restrict__ asym) {
 #pragma clang fp contract(off)
-  __shared__ double sm[VIB_WAVES];
+  __shared__ double sm[4];
   const int b = blockIdx.x;   // the system
   const int tid = threadIdx.x;
-  const VibRange s = vib_range(sel_ptr, b, n_sel);
+  const Range s = checked_range(sel_ptr, b, n_sel);
   const int64_t m3 = 3 * (s.a1 - s.a0), off = d_off[b];
   if (!(s.ok && m3 > 0 && off >= 0 && off <= d_size && m3 * m3 <= d_size - off)) {   // a block outside the buffers: nothing of it is touched
     if (tid == 0) status[b] = 3, asym[b] = __builtin_nan("");
@@ -134,11 +99,8 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_finish_kernel(
     Hm[off + e] = h * (w[s.a0 + r / 3] * w[s.a0 + c / 3]);
     worst = fmax(worst, fabs(x - y));
   }
-  // the maximum over the workgroup (exact in any order)
-  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
-  if ((tid & 63) == 0) sm[tid >> 6] = worst;
-  __syncthreads();
-  if (tid == 0) asym[b] = failed ? nan_d : fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+  worst = block_max(worst, sm);
+  if (tid == 0) asym[b] = failed ? nan_d : worst;
 }
 
 }  // namespace
@@ -146,13 +108,8 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_finish_kernel(
 extern "C" int snet_vib_displace(const double *pos0, int64_t n0, const int32_t *seg_ptr0, int32_t n_sys, const int32_t *desc,
                                  const int32_t *copy_ptr, int32_t n_copies, double delta, double *pos_out, int64_t n_out,
                                  int32_t *status, void *stream) {
-  SNET_REQUIRE(n_sys >= 1 && n_copies >= 1 && n0 >= 0 && n0 < (1ll << 31) && n_out >= 0 && n_out < (1ll << 31),
-               "snet_vib_displace: bad shape");
-  SNET_REQUIRE(pos0 && seg_ptr0 && desc && copy_ptr && pos_out && status, "snet_vib_displace: null argument");
-  vib_displace_kernel<<<(unsigned)n_copies, VIB_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      pos0, n0, seg_ptr0, n_sys, desc, copy_ptr, delta, pos_out, n_out, status);
-  SNET_CHECK_LAUNCH("snet_vib_displace");
-  return 0;
+  return launch_copy_writer("snet_vib_displace", vib_displace_kernel, pos0, n0, seg_ptr0, n_sys, desc, copy_ptr, n_copies, delta,
+                            pos_out, n_out, status, stream);
 }
 
 extern "C" int snet_vib_rows(const float *forces, const double *forces_extra, int64_t n_atoms, const int32_t *seg_ptr,

@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
-"""Bit identity of vibrations_many / phonons_many / elastic_many between two trees of this package (a refactor of their host
-code against its parent commit).
+"""Bit identity of the batched drivers -- vibrations_many / phonons_many / elastic_many, relax_many, md_many, neb_many -- between
+two trees of this package (a refactor of their host code or of their kernels against its parent commit).
 
-    python tools/fd_driver_identity.py TREE OUT.pkl             run the calls below with the package of TREE, pickle the results
-    python tools/fd_driver_identity.py --compare A.pkl B.pkl [--report FILE]    A is the reference
+    python tools/driver_identity.py TREE OUT.pkl             run the calls below with the package of TREE, pickle the results
+    python tools/driver_identity.py --compare A.pkl B.pkl [--report FILE]    A is the reference
 
-Each tree runs in a process of its own; both may share one libsnet_hip.so through SNET_HIP_LIB when no kernel differs.  Inputs:
-tests/helpers.py three_small_systems (seed 0) for the vibrations; its periodic system and two rattled periodic cells of 2 and 3
-atoms, supercell (2,1,1), for phonons and elastic tensors; mini SevenNet-0 shape, random weights seed 0, species Si / O.
+Each tree runs in a process of its own, on the libsnet_hip.so built in it (both may share one through SNET_HIP_LIB when no
+kernel differs).  Inputs: tests/helpers.py three_small_systems (seed 0); its periodic system and two rattled periodic cells of 2
+and 3 atoms (`crystals`) where every system must be periodic; mini SevenNet-0 shape, random weights seed 0, species Si / O.
 Calls: vibrations_many with nfree 2 and 4, all atoms or `indices` for one system, one call or several (max_atoms_per_call);
-phonons_many with a 3-point path, a 2x1x1 mesh, two temperatures and max_q_per_call = 1; elastic_many clamped and with
-relax_ions; each on SevenNetCalculator and on SevenNetD3Calculator with d3_term 'device' and 'host', with and without the
-per-atom virial.  A call that raises is recorded by its exception.  Compared: every key of every result dict -- arrays by
-shape, dtype and np.array_equal with NaN equal to NaN, everything else by == and type -- and the info counters by ==."""
+phonons_many (supercell (2,1,1)) with a 3-point path, a 2x1x1 mesh, two temperatures and max_q_per_call = 1; elastic_many clamped
+and with relax_ions; these with and without the per-atom virial.  relax_many (fmax 0.02, 200 steps) with repack_below 0.5 and 0,
+and with relax_cell (fmax 1e-4) on the crystals; md_many (1 fs, 20 steps, 300 K, seed 0, traj_every 5) with friction 0 and 0.01, and with
+pressure 0 / compressibility 60 on the crystals; neb_many (fmax 1e-4, 50 steps), plain and climbing, on a band of 3 moving images between two rattles
+of the periodic system.  Each on SevenNetCalculator and on SevenNetD3Calculator with d3_term 'device' and, where it is allowed,
+'host'.  A call that raises is recorded by its exception.  Compared: every key of every result dict -- arrays by shape, dtype and
+np.array_equal with NaN equal to NaN, everything else by == and type -- and the info counters by ==."""
 import argparse
 import os
 import pickle
@@ -37,6 +40,7 @@ def crystals(three):
 
 
 def cases(three):
+    """(name, method, info attribute, arguments, keywords, d3_term 'host' allowed, run with the per-atom virial on too)"""
     num = lambda s: [np.array(Z)[t] for t, _, _, _ in s]   # noqa: E731
     mass = lambda s: [np.array([MASS[z] for z in zz]) for zz in num(s)]   # noqa: E731
     geo = lambda s: (np.stack([c for _, _, c, _ in s]), np.array([p for _, _, _, p in s]))   # noqa: E731
@@ -46,15 +50,34 @@ def cases(three):
             for b_name, budget in BUDGETS.items():
                 yield (f'vibrations_many(nfree={nfree}, {idx_name}, {b_name})', 'vibrations_many', 'vib_info',
                        (num(three), [p for _, p, _, _ in three], mass(three)) + geo(three),
-                       dict(nfree=nfree, indices=idx, max_atoms_per_call=budget), True)
+                       dict(nfree=nfree, indices=idx, max_atoms_per_call=budget), True, True)
     path = np.array([[0.0, 0.0, 0.0], [0.25, 0.0, 0.0], [0.5, 0.0, 0.0]])
     for b_name, budget in BUDGETS.items():
         yield (f'phonons_many(path 3, mesh 2x1x1, 2 temperatures, max_q_per_call=1, {b_name})', 'phonons_many', 'phonon_info',
                (num(cry), [p for _, p, _, _ in cry], mass(cry)) + geo(cry) + ((2, 1, 1),),
-               dict(qpoints=path, mesh=(2, 1, 1), temperatures=[0.0, 300.0], max_q_per_call=1, max_atoms_per_call=budget, want_modes=True), True)
+               dict(qpoints=path, mesh=(2, 1, 1), temperatures=[0.0, 300.0], max_q_per_call=1, max_atoms_per_call=budget, want_modes=True), True, True)
         for relax_ions in (False, True):
             yield (f'elastic_many(relax_ions={relax_ions}, {b_name})', 'elastic_many', 'elastic_info',
-                   (num(cry), [p for _, p, _, _ in cry]) + geo(cry), dict(relax_ions=relax_ions, max_atoms_per_call=budget), False)
+                   (num(cry), [p for _, p, _, _ in cry]) + geo(cry), dict(relax_ions=relax_ions, max_atoms_per_call=budget), False, True)
+    pos = lambda s: [p for _, p, _, _ in s]   # noqa: E731
+    for repack in (0.5, 0):
+        yield (f'relax_many(repack_below={repack})', 'relax_many', 'relax_info', (num(three), pos(three)) + geo(three),
+               dict(fmax=0.02, steps=200, repack_below=repack), True, False)
+    yield ('relax_many(relax_cell=True)', 'relax_many', 'relax_info', (num(cry), pos(cry)) + geo(cry),
+           dict(fmax=1e-4, steps=200, relax_cell=True), False, False)   # (the model's forces alone are below 0.02)
+    md = dict(dt=1.0, steps=20, temperature=300.0, seed=0, traj_every=5)
+    for friction in (0.0, 0.01):
+        yield (f'md_many(friction={friction})', 'md_many', 'md_info', (num(three), pos(three), mass(three)) + geo(three),
+               dict(md, friction=friction), True, False)
+    yield ('md_many(pressure=0.0, compressibility=60.0)', 'md_many', 'md_info', (num(cry), pos(cry), mass(cry)) + geo(cry),
+           dict(md, friction=0.01, pressure=0.0, compressibility=60.0), False, False)
+    t, p0, cell, pbc = three[0]   # the periodic system: a band of 3 moving images between two rattles of it
+    rng = np.random.default_rng(1)
+    ends = [p0 + rng.normal(0, 0.05, p0.shape) for _ in range(2)]
+    band = ends[0][None] + np.linspace(0.0, 1.0, 5)[:, None, None] * (ends[1] - ends[0])[None]
+    for climb in (False, True):
+        yield (f'neb_many(climb={climb})', 'neb_many', 'neb_info', ([np.array(Z)[t]], [band], np.array(cell)[None], np.array([pbc])),
+               dict(fmax=1e-4, steps=50, climb=climb), True, False)
 
 
 def run(tree, out_path):
@@ -75,7 +98,9 @@ def run(tree, out_path):
     record = {}
     for atomic_virial in (False, True):
         snet.compute_atomic_virial = d3.calcs[0].compute_atomic_virial = atomic_virial
-        for name, method, info, args, kw, host_allowed in cases(three):
+        for name, method, info, args, kw, host_allowed, both_virials in cases(three):
+            if atomic_virial and not both_virials:
+                continue
             for calc_name, calc, extra in (('snet', snet, {}), ('snet_d3[device]', d3, dict(d3_term='device')), ('snet_d3[host]', d3, dict(d3_term='host'))):
                 if calc is d3 and extra['d3_term'] == 'host' and not host_allowed:
                     continue
@@ -119,7 +144,8 @@ def compare(ref_path, new_path, report):
             lines.append(f'    raises {want}')
         else:
             arrays = {k: [r[k].shape for r in want[0]] for k, v in want[0][0].items() if isinstance(v, np.ndarray)}
-            lines += [f'    info {want[1]}', f'    arrays per system {arrays}']
+            other = {k: [r[k] for r in want[0]] for k, v in want[0][0].items() if isinstance(v, (bool, int, str))}
+            lines += [f'    info {want[1]}', f'    arrays per system {arrays}', f'    {other}']
         diff = differences(want, new.get(key), key)
         bad += diff
         lines += [f'    DIFFERS {d}' for d in diff] or ['    -> identical']
