@@ -849,60 +849,72 @@ int layer0_select(snet_model *m, const int32_t *types, int64_t NT, hipStream_t s
   *out = &it->second;
   return 0;
 }
-}  // namespace
 
-extern "C" int64_t snet_model_eval_syncs(const snet_model *m) { return m ? m->eval_syncs : -1; }
+// w: radial weights [WR, wn], or (fused layers) hidden activations h2 [WR, 64] and wd = h2' = d h2 / d|r| [WR, 64]
+struct Saved { float *h, *w, *y, *wd; };
 
-extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, const int32_t *types,
-                               const int32_t *types_host, const int32_t *row_ptr, const int32_t *src,
-                               const int32_t *col_ptr, const int32_t *eperm, const float *edge_vec,
-                               const int32_t *w_row, const int32_t *pair_edge, int64_t n_pairs, double *energy,
-                               float *e_atom, float *dE_dr, float *forces, double *virial, float *virial_atom,
-                               void *stream) {
-  SNET_REQUIRE(m != nullptr, "snet_model_eval: null model");
-  SNET_REQUIRE(NT >= N && N > 0 && E >= 0, "snet_model_eval: need n_total >= n_local > 0 and n_edges >= 0");
-  SNET_REQUIRE(NT == N || (m->halo_fwd && m->halo_rev), "snet_model_eval: ghost atoms need halo callbacks");
-  // The exchange is a collective of send/recv pairs: a rank without ghost rows of its own may still own rows its
-  // peers wait for (slab / cluster systems whose only ghosts are periodic self-images), so an installed halo is
-  // called on every layer whatever NT - N is (snet_halo_* handles n_ghost == 0)
-  const bool has_halo = m->halo_fwd != nullptr && m->halo_rev != nullptr;
-  const bool pairs = w_row != nullptr && E > 0;
-  SNET_REQUIRE(!pairs || (pair_edge != nullptr && n_pairs > 0 && n_pairs <= E),
-               "snet_model_eval: w_row needs pair_edge and 0 < n_pairs <= n_edges");
-  const int64_t WR = pairs ? n_pairs : E;  // rows of each layer's radial-weight matrix
+// What one evaluation's phases hand on to each other (the `c` of engine.py's phase methods).  Data only, built per call.
+struct Eval {
+  // the call's arguments
+  int64_t NT, N, E;
+  const int32_t *types, *types_host, *row_ptr, *src, *col_ptr, *eperm;
+  const float *edge_vec;
+  const int32_t *w_row, *pair_edge;
+  int64_t n_pairs;
+  double *energy;
+  float *e_atom, *dE_dr, *forces;
+  double *virial;
+  float *virial_atom;
+  void *stream;
+  // sizes and flags (begin)
+  hipStream_t st = nullptr;
+  int nb = 0, nsh = 0, Lc = 0;
+  size_t dmax = 0, wn_max = 0;   // widest node feature row, widest radial-weight row
+  bool has_halo = false, pairs = false;
+  int64_t WR = 0;   // rows of each layer's radial-weight matrix
   bool any_fused = false, any_transposed = false, need_sh_t = false;
   bool need_tiles[2] = {false, false};   // per work-list format of the fused reverse kernels
-  // the last layer's reverse pass as one source-grouped launch (its radial gradient from h2', like a tangent-mode layer)
-  const bool ll_on = m->ll_mode && m->layers.back().merged != nullptr;
-  for (auto &L : m->layers) {
-    any_fused |= L.fused != nullptr;
-    any_transposed |= L.tfused != nullptr;
-    need_sh_t |= L.tfused != nullptr && !(ll_on && &L == &m->layers.back());   // (the merged launch reads sh through eperm)
-    if (L.fused) need_tiles[L.tile_mode != 0] = true;
-  }
-  // the second stream only carries the separate radial-MLP kernels (same policy as engine.py)
-  bool ov = m->overlap && E > 0 && E <= OVERLAP_MAX_EDGES && !any_fused;
-  if (ov && m->side == nullptr) {  // created on first use; any failure just keeps everything on one stream
-    bool ok = hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&m->ev_main, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&m->ev_bwd[0], hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&m->ev_bwd[1], hipEventDisableTiming) == hipSuccess;
-    m->ev_w.resize(m->n_layers, nullptr);
-    for (int t = 0; ok && t < m->n_layers; ++t) ok = hipEventCreateWithFlags(&m->ev_w[t], hipEventDisableTiming) == hipSuccess;
-    if (!ok) m->overlap = ov = false;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int nb = m->n_basis, nsh = (m->lmax + 1) * (m->lmax + 1);
-  const int Lc = m->n_layers;
+  bool ll_on = false;     // the last layer's reverse pass as one source-grouped launch (its radial gradient from h2', like a tangent-mode layer)
+  bool ov = false;        // the second stream carries the separate radial-MLP kernels (same policy as engine.py)
+  bool lib_halo = false, hsplit = false;   // interior / boundary split around the library's own exchange
+  int64_t n_int = 0;      // rows [0, n_int) have no ghost source
+  bool all_tangent = true;   // every layer's radial gradient reaches g_vec inside its reverse kernel: no g_emb, no snet_edge_embed_bwd
+  bool topo_hit = false;
+  const snet_model::L0Plan *l0 = nullptr;   // layer 0's reverse pass from per-atom products, where its shape and this graph's species allow it
+  size_t l0_scratch = 0;                    // Bm [N, nsh, slots, 64]
+  // device pointers
+  snet_edge_params ep{};
+  float *emb = nullptr;
+  const float *emb_w = nullptr;  // rows the radial MLP runs on: one per undirected pair when a pair map is given
+  float *sh = nullptr, *dsh = nullptr, *g_vec = nullptr, *g_emb = nullptr;
+  float *x = nullptr, *x2 = nullptr;   // layer 0 reads the species tables, not x
+  std::vector<Saved> saved;
+  int32_t *tile_ptr = nullptr, *tile_node = nullptr;   // 16-edge tiles of the CSR segments: work list of the fused reverse kernels
+  int64_t n_tiles = 0;
+  int32_t *tile_ptr_b = nullptr;   // boundary rows' tiles: tile_node + tile_k, tile pointers re-based by -tile_k
+  int64_t tile_k = 0;
+  int32_t *ptile_e0 = nullptr, *ptile_nodes = nullptr;   // packed tiles: the interior rows' [0, ptile_k) in front of the boundary rows'
+  int64_t pn_tiles = 0, ptile_k = 0;
+  int32_t *center_t = nullptr, *w_row_t = nullptr;  // edges grouped by source (transposed scalar convolution)
+  float *sh_t = nullptr;
+  float *gw_buf[2] = {nullptr, nullptr};   // g_w double buffer (its reader runs on the side stream)
+  bool gw_busy[2] = {false, false};
+  std::vector<float *> x_max_of;   // fp16 operands of the fused reverse kernels: per layer, the bounds of its source rows
+  size_t mark = 0, mark2 = 0;      // arena offsets where the forward / the reverse layers' transient regions start
+  float *g_x = nullptr, *gx_next = nullptr;   // gradient rows of the reverse pass (x / x2 again)
+};
 
-  // ---- per-species row lists (FCTP self-connection only)
+// ---- per-species row lists (FCTP self-connection only)
+int species_rows(snet_model *m, Eval &e) {
+  const int64_t N = e.N;
+  const int32_t *types_host = e.types_host;
   bool need_rows = false;
   for (auto &L : m->layers) need_rows |= L.sc.n_species > 0;
-  if (need_rows) {
-    SNET_REQUIRE(types_host != nullptr, "snet_model_eval: this model needs types_host (per-species self-connection)");
-    const bool same_types = (int64_t)m->types_prev.size() == N && m->species_rows != nullptr &&
-                            memcmp(m->types_prev.data(), types_host, (size_t)N * 4) == 0;
-    if (!same_types) {
+  if (!need_rows) return 0;
+  SNET_REQUIRE(types_host != nullptr, "snet_model_eval: this model needs types_host (per-species self-connection)");
+  const bool same_types = (int64_t)m->types_prev.size() == N && m->species_rows != nullptr &&
+                          memcmp(m->types_prev.data(), types_host, (size_t)N * 4) == 0;
+  if (!same_types) {
     m->species_rows_host.assign(m->n_species, {});
     for (int64_t i = 0; i < N; ++i) {
       SNET_REQUIRE(types_host[i] >= 0 && types_host[i] < m->n_species, "snet_model_eval: species index out of range");
@@ -921,48 +933,204 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       m->species_off[s] = o;
       m->species_cnt[s] = (int64_t)v.size();
       if (!v.empty())
-        SNET_REQUIRE(hipMemcpyAsync(m->species_rows + o, v.data(), v.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess,
+        SNET_REQUIRE(hipMemcpyAsync(m->species_rows + o, v.data(), v.size() * 4, hipMemcpyHostToDevice, e.st) == hipSuccess,
                      "snet_model_eval: upload of species rows failed");
       o += (int64_t)v.size();
     }
-    SNET_REQUIRE(hipStreamSynchronize(st) == hipSuccess, "snet_model_eval: sync");  // host vectors are reused
+    SNET_REQUIRE(hipStreamSynchronize(e.st) == hipSuccess, "snet_model_eval: sync");  // host vectors are reused
     ++m->eval_syncs;
     m->types_prev.assign(types_host, types_host + N);
-    }
   }
+  return 0;
+}
 
-  // ---- layer 0's reverse pass from per-atom products (where its shape and this graph's species allow it)
-  const snet_model::L0Plan *l0 = nullptr;
-  if (m->l0_mode && m->l0_shape_ok && E > 0)
-    if (int rc0 = layer0_select(m, types, NT, st, &l0)) return rc0;
-  const size_t l0_scratch = l0 ? (size_t)snet_layer0_scratch_size(l0->plan, N) + 64 : 0;   // Bm [N, nsh, slots, 64]
-
-  // ---- arena sizing
+// ---- arena sizing: a function of the sizes and flags alone
+size_t arena_bytes(const snet_model *m, const Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E, WR = e.WR;
+  const int nb = e.nb, nsh = e.nsh;
+  const size_t dmax = e.dmax, wn_max = e.wn_max, l0_scratch = e.l0_scratch;
   size_t need = 0;
   auto add = [&](size_t n) { need += ((n * 4 + 255) / 256) * 256; };
-  size_t dmax = (size_t)m->d0, trans = 0;
+  size_t trans = 0;
   add((size_t)E * nb); add((size_t)E * nsh); add((size_t)E * nsh * 3); add((size_t)E * 3); add((size_t)E * nb);
   add((size_t)WR * nb); add((size_t)WR * nb);  // emb per radial row, its derivative with respect to |r|
   for (auto &L : m->layers) {
     if (L.fused) add((size_t)WR * 64);  // h2' = d h2 / d|r| (tangent mode of the fused reverse kernel)
-    dmax = dmax > (size_t)L.dout ? dmax : (size_t)L.dout;
     add((size_t)NT * L.dx); add(L.fused ? (size_t)WR * 64 : (size_t)WR * L.wn); add((size_t)N * L.gin);  // saved h, w | h2, y
     add((size_t)NT + 64);  // x_max (kept through the reverse pass)
     const size_t t = ((size_t)N * L.gin + 64) * 2 + (size_t)N * L.dmid * 2 + (size_t)E * (L.fused ? 64 : L.wn) + (size_t)E * L.dx +
                      (size_t)NT * L.dx * 2 + (size_t)N * L.dout + (size_t)NT + (size_t)N + 4096 + l0_scratch;  // + x_max, g_max
     trans = trans > t ? trans : t;
   }
-  size_t wn_max = 0;
-  for (auto &L : m->layers) wn_max = wn_max > (size_t)L.wn ? wn_max : (size_t)L.wn;
-  if (ov) { add((size_t)E * wn_max); add((size_t)E * wn_max); }  // g_w double buffer (its reader runs on the side stream)
-  if (need_tiles[0]) { add((size_t)N + 64); add((size_t)N + (size_t)E / 16 + 64); }  // tile_ptr, tile_node
-  if (need_tiles[1]) { add((size_t)N + (size_t)E / 16 + 64); add(2 * ((size_t)N + (size_t)E / 16 + 64)); }  // packed: tile_e0, tile_nodes
-  if (any_transposed) { add((size_t)E + 64); add((size_t)E + 64); add((size_t)E * nsh + 64); }  // center_t, w_row_t, sh_t
+  if (e.ov) { add((size_t)E * wn_max); add((size_t)E * wn_max); }  // g_w double buffer (its reader runs on the side stream)
+  if (e.need_tiles[0]) { add((size_t)N + 64); add((size_t)N + (size_t)E / 16 + 64); }  // tile_ptr, tile_node
+  if (e.need_tiles[1]) { add((size_t)N + (size_t)E / 16 + 64); add(2 * ((size_t)N + (size_t)E / 16 + 64)); }  // packed: tile_e0, tile_nodes
+  if (e.any_transposed) { add((size_t)E + 64); add((size_t)E + 64); add((size_t)E * nsh + 64); }  // center_t, w_row_t, sh_t
   add((size_t)NT * dmax * 2 + 256); add((size_t)N * (m->ro1.dim_out + 8) * 2); add(trans + 64 * 1024);
   for (size_t i = 0; i + 1 < m->fcn_dims.size(); ++i) {   // readout_as_fcn: z_i, a_i forward, the gradient rows in reverse
     add((size_t)N * m->fcn_dims[i + 1] + 64); add((size_t)N * m->fcn_dims[i + 1] + 64); add((size_t)N * m->fcn_dims[i] + 64);
   }
   need += 1 << 20;
+  return need;
+}
+
+// The two buffers of a work list that depends on the edge list only: the model's cached pair c0 / c1 -- freed and allocated anew, bytes0 /
+// bytes1, when `grow` (the caller found them too small and has set their new capacities) -- or, cache off, n0 / n1 words of the arena
+int topo_lists(snet_model *m, bool grow, int32_t *&c0, size_t bytes0, int32_t *&c1, size_t bytes1, size_t n0, size_t n1, int32_t *&p0,
+               int32_t *&p1) {
+  if (!m->topo_cache) {
+    p0 = reinterpret_cast<int32_t *>(m->arena.f(n0));
+    p1 = reinterpret_cast<int32_t *>(m->arena.f(n1));
+    return 0;
+  }
+  if (grow) {
+    if (c0) (void)hipFree(c0);
+    if (c1) (void)hipFree(c1);
+    c0 = c1 = nullptr;
+    SNET_REQUIRE(hipMalloc((void **)&c0, bytes0) == hipSuccess && hipMalloc((void **)&c1, bytes1) == hipSuccess, "snet_model_eval: alloc");
+  }
+  p0 = c0;
+  p1 = c1;
+  return 0;
+}
+
+// ---- topology-only work: rebuilt unless the cache holds it for exactly these index arrays
+int topology(snet_model *m, Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E, n_int = e.n_int;
+  const int32_t *row_ptr = e.row_ptr;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  int rc;
+  const snet_model::TopoKey key{NT, N, E, row_ptr, e.src, e.eperm, e.pairs ? e.w_row : nullptr};
+  const bool topo_hit = e.topo_hit = m->topo_cache && m->topo_valid && memcmp(&key, &m->topo_key, sizeof key) == 0;
+  if (e.need_tiles[0] && E > 0) {  // 16-edge tiles of the CSR segments
+    const size_t n_ptr = (size_t)N + 64, n_node = (size_t)N + (size_t)E / 16 + 64;
+    const bool grow = m->topo_cache && (m->c_node_cap < n_ptr || m->c_tile_cap < n_node);
+    if (grow) {
+      m->c_node_cap = n_ptr;
+      m->c_tile_cap = n_node;
+    }
+    if ((rc = topo_lists(m, grow, m->c_tile_ptr, m->c_node_cap * 4, m->c_tile_node, m->c_tile_cap * 4, n_ptr, n_node, e.tile_ptr, e.tile_node)))
+      return rc;
+    if (topo_hit) {
+      e.n_tiles = m->c_n_tiles;
+    } else {
+      if ((rc = snet_edge_tiles(row_ptr, N, e.tile_ptr, e.tile_node, N + E / 16 + 1, &e.n_tiles, st))) return rc;
+      ++m->eval_syncs;   // (snet_edge_tiles reads the tile count back)
+      m->c_n_tiles = e.n_tiles;
+    }
+  }
+  // packed tiles: built per row range when the step is split (no tile straddles the cut; the interior list's end sentinel is the
+  // first boundary tile's first edge, so the two lists are one)
+  if (e.need_tiles[1] && E > 0) {
+    const size_t cap = (size_t)N + (size_t)E / 16 + 2;
+    const bool grow = m->topo_cache && m->c_ptile_cap < cap;
+    if (grow) m->c_ptile_cap = cap + cap / 8 + 64;
+    if ((rc = topo_lists(m, grow, m->c_ptile_e0, (m->c_ptile_cap + 1) * 4, m->c_ptile_nodes, m->c_ptile_cap * 8, (size_t)N + (size_t)E / 16 + 64,
+                         2 * ((size_t)N + (size_t)E / 16 + 64), e.ptile_e0, e.ptile_nodes)))
+      return rc;
+    if (topo_hit) {
+      e.pn_tiles = m->c_pn_tiles;
+      e.ptile_k = m->c_ptile_k;
+    } else {
+      const int64_t cut = n_int > 0 && n_int < N ? n_int : 0;   // (whether or not this evaluation is split: one tiling per graph, like engine.py)
+      int64_t n_bound = 0;
+      if (cut > 0) {
+        if ((rc = snet_edge_tiles_packed(row_ptr, 0, cut, e.ptile_e0, e.ptile_nodes, (int64_t)cap, &e.ptile_k, st))) return rc;
+        ++m->eval_syncs;   // (the builder reads the tile count back)
+      }
+      if ((rc = snet_edge_tiles_packed(row_ptr, cut, N, e.ptile_e0 + e.ptile_k, e.ptile_nodes + 2 * e.ptile_k, (int64_t)cap - e.ptile_k, &n_bound,
+                                       st)))
+        return rc;
+      ++m->eval_syncs;
+      e.pn_tiles = e.ptile_k + n_bound;
+      m->c_pn_tiles = e.pn_tiles;
+      m->c_ptile_k = e.ptile_k;
+    }
+  }
+  if (e.any_transposed && E > 0) {  // edges grouped by source (transposed scalar convolution)
+    const bool grow = m->topo_cache && m->c_edge_cap < (size_t)E + 64;
+    if (grow) m->c_edge_cap = (size_t)E + 64;
+    if ((rc = topo_lists(m, grow, m->c_center_t, m->c_edge_cap * 4, m->c_w_row_t, m->c_edge_cap * 4, (size_t)E + 64, (size_t)E + 64, e.center_t,
+                         e.w_row_t)))
+      return rc;
+    if (e.need_sh_t) e.sh_t = A.f((size_t)E * e.nsh + 64);
+    if (!topo_hit && (rc = snet_edges_by_source(row_ptr, N, e.eperm, e.pairs ? e.w_row : nullptr, E, e.center_t, e.w_row_t, st))) return rc;
+    if (e.need_sh_t && (rc = snet_gather_rows(e.sh, e.eperm, e.sh_t, E, e.nsh, st))) return rc;   // (the harmonics change with the positions: every step)
+  }
+  if (e.hsplit && e.need_tiles[0]) {   // boundary rows' tiles
+    if (m->c_tile_ptr_b_cap < (size_t)N + 64) {
+      if (m->c_tile_ptr_b) (void)hipFree(m->c_tile_ptr_b);
+      m->c_tile_ptr_b = nullptr;
+      m->c_tile_ptr_b_cap = (size_t)N + 64;
+      m->c_split_valid = false;
+      SNET_REQUIRE(hipMalloc((void **)&m->c_tile_ptr_b, m->c_tile_ptr_b_cap * 4) == hipSuccess, "snet_model_eval: alloc");
+    }
+    e.tile_ptr_b = m->c_tile_ptr_b;
+    if (topo_hit && m->c_split_valid) {
+      e.tile_k = m->c_tile_k;
+    } else {
+      int32_t k32 = 0;
+      SNET_REQUIRE(hipMemcpyAsync(&k32, e.tile_ptr + n_int, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                       hipStreamSynchronize(st) == hipSuccess, "snet_model_eval: tile readback failed");
+      ++m->eval_syncs;
+      e.tile_k = m->c_tile_k = k32;
+      if ((rc = snet_i32_shift(e.tile_ptr, -k32, e.tile_ptr_b, N + 1, st))) return rc;
+      m->c_split_valid = true;
+    }
+  }
+  if (!topo_hit && !(e.hsplit && e.need_tiles[0])) m->c_split_valid = false;   // a new graph was tiled without its boundary sub-list
+  if (m->topo_cache) {
+    m->topo_key = key;
+    m->topo_valid = true;
+  }
+  return 0;
+}
+
+// ---- engine.py::_begin: checks and flags, row lists, layer 0's plan, the arena, the edge embedding, the topology's work lists, the radial
+// networks' hidden layers
+int begin(snet_model *m, Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E;
+  SNET_REQUIRE(NT >= N && N > 0 && E >= 0, "snet_model_eval: need n_total >= n_local > 0 and n_edges >= 0");
+  SNET_REQUIRE(NT == N || (m->halo_fwd && m->halo_rev), "snet_model_eval: ghost atoms need halo callbacks");
+  // The exchange is a collective of send/recv pairs: a rank without ghost rows of its own may still own rows its
+  // peers wait for (slab / cluster systems whose only ghosts are periodic self-images), so an installed halo is
+  // called on every layer whatever NT - N is (snet_halo_* handles n_ghost == 0)
+  e.has_halo = m->halo_fwd != nullptr && m->halo_rev != nullptr;
+  const bool pairs = e.pairs = e.w_row != nullptr && E > 0;
+  SNET_REQUIRE(!pairs || (e.pair_edge != nullptr && e.n_pairs > 0 && e.n_pairs <= E),
+               "snet_model_eval: w_row needs pair_edge and 0 < n_pairs <= n_edges");
+  const int64_t WR = e.WR = pairs ? e.n_pairs : E;
+  e.ll_on = m->ll_mode && m->layers.back().merged != nullptr;
+  e.dmax = (size_t)m->d0;
+  for (auto &L : m->layers) {
+    e.any_fused |= L.fused != nullptr;
+    e.any_transposed |= L.tfused != nullptr;
+    e.need_sh_t |= L.tfused != nullptr && !(e.ll_on && &L == &m->layers.back());   // (the merged launch reads sh through eperm)
+    if (L.fused) e.need_tiles[L.tile_mode != 0] = true;
+    e.dmax = e.dmax > (size_t)L.dout ? e.dmax : (size_t)L.dout;
+    e.wn_max = e.wn_max > (size_t)L.wn ? e.wn_max : (size_t)L.wn;
+  }
+  e.ov = m->overlap && E > 0 && E <= OVERLAP_MAX_EDGES && !e.any_fused;
+  if (e.ov && m->side == nullptr) {  // created on first use; any failure just keeps everything on one stream
+    bool ok = hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&m->ev_main, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&m->ev_bwd[0], hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&m->ev_bwd[1], hipEventDisableTiming) == hipSuccess;
+    m->ev_w.resize(m->n_layers, nullptr);
+    for (int t = 0; ok && t < m->n_layers; ++t) ok = hipEventCreateWithFlags(&m->ev_w[t], hipEventDisableTiming) == hipSuccess;
+    if (!ok) m->overlap = e.ov = false;
+  }
+  hipStream_t st = e.st = static_cast<hipStream_t>(e.stream);
+  const int nb = e.nb = m->n_basis, nsh = e.nsh = (m->lmax + 1) * (m->lmax + 1);
+  const int Lc = e.Lc = m->n_layers;
+  int rc;
+  if ((rc = species_rows(m, e))) return rc;
+  if (m->l0_mode && m->l0_shape_ok && E > 0)
+    if (int rc0 = layer0_select(m, e.types, NT, st, &e.l0)) return rc0;
+  e.l0_scratch = e.l0 ? (size_t)snet_layer0_scratch_size(e.l0->plan, N) + 64 : 0;
+
+  const size_t need = arena_bytes(m, e);
   if (m->arena.cap < need) {
     if (m->arena.base) (void)hipFree(m->arena.base);
     m->arena.base = nullptr;
@@ -973,228 +1141,117 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
   Arena &A = m->arena;
   A.off = 0;
 
-  snet_edge_params ep{m->cutoff, m->n_basis, m->cutoff_kind, m->poly_p, m->cutoff_on, m->lmax, m->normalize};
-  float *emb = A.f((size_t)E * nb), *sh = A.f((size_t)E * nsh), *dsh = A.f((size_t)E * nsh * 3);
-  float *g_vec = dE_dr ? dE_dr : A.f((size_t)E * 3), *g_emb = A.f((size_t)E * nb);
-  int rc;
-  if ((rc = snet_edge_embed_fwd(&ep, m->coeffs.data(), edge_vec, E, emb, sh, dsh, st))) return rc;
-  const float *emb_w = emb;  // rows the radial MLP runs on: one per undirected pair when a pair map is given
+  e.ep = snet_edge_params{m->cutoff, m->n_basis, m->cutoff_kind, m->poly_p, m->cutoff_on, m->lmax, m->normalize};
+  e.emb = A.f((size_t)E * nb);
+  e.sh = A.f((size_t)E * nsh);
+  e.dsh = A.f((size_t)E * nsh * 3);
+  e.g_vec = e.dE_dr ? e.dE_dr : A.f((size_t)E * 3);
+  e.g_emb = A.f((size_t)E * nb);
+  if ((rc = snet_edge_embed_fwd(&e.ep, m->coeffs.data(), e.edge_vec, E, e.emb, e.sh, e.dsh, st))) return rc;
+  e.emb_w = e.emb;
   if (pairs) {
-    float *ep = A.f((size_t)WR * nb);
-    if ((rc = snet_gather_rows(emb, pair_edge, ep, WR, nb, st))) return rc;
-    emb_w = ep;
+    float *emb_p = A.f((size_t)WR * nb);
+    if ((rc = snet_gather_rows(e.emb, e.pair_edge, emb_p, WR, nb, st))) return rc;
+    e.emb_w = emb_p;
   }
-  float *x = A.f((size_t)NT * dmax), *x2 = A.f((size_t)NT * dmax);  // layer 0 reads the species tables, not x
+  e.x = A.f((size_t)NT * e.dmax);
+  e.x2 = A.f((size_t)NT * e.dmax);
 
-  // w: radial weights [WR, wn], or (fused layers) hidden activations h2 [WR, 64] and wd = h2' = d h2 / d|r| [WR, 64]
-  struct Saved { float *h, *w, *y, *wd; };
-  std::vector<Saved> saved(Lc);
-  bool all_tangent = true;   // every layer's radial gradient reaches g_vec inside its reverse kernel: no g_emb, no snet_edge_embed_bwd
+  e.saved.resize(Lc);
   for (int t = 0; t < Lc; ++t) {
-    saved[t].h = A.f((size_t)NT * m->layers[t].dx);
-    saved[t].w = A.f(m->layers[t].fused ? (size_t)WR * 64 : (size_t)WR * m->layers[t].wn);
-    const bool tg = m->layers[t].fused != nullptr && (snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0 || (t == 0 && l0 != nullptr) ||
-                                                          (t == Lc - 1 && ll_on));
-    saved[t].wd = tg ? A.f((size_t)WR * 64) : nullptr;
-    all_tangent = all_tangent && tg;
-    saved[t].y = A.f((size_t)N * m->layers[t].gin);
+    Saved &s = e.saved[t];
+    s.h = A.f((size_t)NT * m->layers[t].dx);
+    s.w = A.f(m->layers[t].fused ? (size_t)WR * 64 : (size_t)WR * m->layers[t].wn);
+    const bool tg = m->layers[t].fused != nullptr && (snet_fused_plan_prefers_tangent(m->layers[t].fused) != 0 || (t == 0 && e.l0 != nullptr) ||
+                                                          (t == Lc - 1 && e.ll_on));
+    s.wd = tg ? A.f((size_t)WR * 64) : nullptr;
+    e.all_tangent = e.all_tangent && tg;
+    s.y = A.f((size_t)N * m->layers[t].gin);
   }
-  // topology-only work: rebuilt unless the cache holds it for exactly these index arrays
-  const snet_model::TopoKey key{NT, N, E, row_ptr, src, eperm, pairs ? w_row : nullptr};
-  const bool topo_hit = m->topo_cache && m->topo_valid && memcmp(&key, &m->topo_key, sizeof key) == 0;
   // interior / boundary split: the library's own exchange (stream-safe) on a second stream, rows [0, n_int) have no ghost source
-  const bool lib_halo = has_halo && m->halo_fwd == &snet_halo_forward && m->halo_rev == &snet_halo_reverse;
-  const int64_t n_int = m->n_interior;
-  bool hsplit = lib_halo && n_int > 0 && n_int < N && E > 0 && any_fused && getenv("SNET_NO_HALO_SPLIT") == nullptr;
-  if (hsplit && m->halo_stream == nullptr) {
-    hsplit = hipStreamCreateWithFlags(&m->halo_stream, hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_h0, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&m->ev_h1, hipEventDisableTiming) == hipSuccess;
+  e.lib_halo = e.has_halo && m->halo_fwd == &snet_halo_forward && m->halo_rev == &snet_halo_reverse;
+  e.n_int = m->n_interior;
+  e.hsplit = e.lib_halo && e.n_int > 0 && e.n_int < N && E > 0 && e.any_fused && getenv("SNET_NO_HALO_SPLIT") == nullptr;
+  if (e.hsplit && m->halo_stream == nullptr) {
+    e.hsplit = hipStreamCreateWithFlags(&m->halo_stream, hipStreamNonBlocking) == hipSuccess &&
+               hipEventCreateWithFlags(&m->ev_h0, hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&m->ev_h1, hipEventDisableTiming) == hipSuccess;
   }
-  int32_t *tile_ptr = nullptr, *tile_node = nullptr;
-  int64_t n_tiles = 0;
-  if (need_tiles[0] && E > 0) {  // 16-edge tiles of the CSR segments: work list of the fused reverse kernels
-    if (m->topo_cache) {
-      if (m->c_node_cap < (size_t)N + 64 || m->c_tile_cap < (size_t)N + (size_t)E / 16 + 64) {
-        if (m->c_tile_ptr) (void)hipFree(m->c_tile_ptr);
-        if (m->c_tile_node) (void)hipFree(m->c_tile_node);
-        m->c_tile_ptr = m->c_tile_node = nullptr;
-        m->c_node_cap = (size_t)N + 64;
-        m->c_tile_cap = (size_t)N + (size_t)E / 16 + 64;
-        SNET_REQUIRE(hipMalloc((void **)&m->c_tile_ptr, m->c_node_cap * 4) == hipSuccess &&
-                         hipMalloc((void **)&m->c_tile_node, m->c_tile_cap * 4) == hipSuccess, "snet_model_eval: alloc");
-      }
-      tile_ptr = m->c_tile_ptr;
-      tile_node = m->c_tile_node;
-    } else {
-      tile_ptr = reinterpret_cast<int32_t *>(A.f((size_t)N + 64));
-      tile_node = reinterpret_cast<int32_t *>(A.f((size_t)N + (size_t)E / 16 + 64));
-    }
-    if (topo_hit) {
-      n_tiles = m->c_n_tiles;
-    } else {
-      if ((rc = snet_edge_tiles(row_ptr, N, tile_ptr, tile_node, N + E / 16 + 1, &n_tiles, st))) return rc;
-      ++m->eval_syncs;   // (snet_edge_tiles reads the tile count back)
-      m->c_n_tiles = n_tiles;
-    }
-  }
-  // packed tiles: built per row range when the step is split (no tile straddles the cut; the interior list's end sentinel is the
-  // first boundary tile's first edge, so the two lists are one)
-  int32_t *ptile_e0 = nullptr, *ptile_nodes = nullptr;
-  int64_t pn_tiles = 0, ptile_k = 0;
-  if (need_tiles[1] && E > 0) {
-    const size_t cap = (size_t)N + (size_t)E / 16 + 2;
-    if (m->topo_cache) {
-      if (m->c_ptile_cap < cap) {
-        if (m->c_ptile_e0) (void)hipFree(m->c_ptile_e0);
-        if (m->c_ptile_nodes) (void)hipFree(m->c_ptile_nodes);
-        m->c_ptile_e0 = m->c_ptile_nodes = nullptr;
-        m->c_ptile_cap = cap + cap / 8 + 64;
-        SNET_REQUIRE(hipMalloc((void **)&m->c_ptile_e0, (m->c_ptile_cap + 1) * 4) == hipSuccess &&
-                         hipMalloc((void **)&m->c_ptile_nodes, m->c_ptile_cap * 8) == hipSuccess, "snet_model_eval: alloc");
-      }
-      ptile_e0 = m->c_ptile_e0;
-      ptile_nodes = m->c_ptile_nodes;
-    } else {
-      ptile_e0 = reinterpret_cast<int32_t *>(A.f((size_t)N + (size_t)E / 16 + 64));
-      ptile_nodes = reinterpret_cast<int32_t *>(A.f(2 * ((size_t)N + (size_t)E / 16 + 64)));
-    }
-    if (topo_hit) {
-      pn_tiles = m->c_pn_tiles;
-      ptile_k = m->c_ptile_k;
-    } else {
-      const int64_t cut = n_int > 0 && n_int < N ? n_int : 0;   // (whether or not this evaluation is split: one tiling per graph, like engine.py)
-      int64_t nb = 0;
-      if (cut > 0) {
-        if ((rc = snet_edge_tiles_packed(row_ptr, 0, cut, ptile_e0, ptile_nodes, (int64_t)cap, &ptile_k, st))) return rc;
-        ++m->eval_syncs;   // (the builder reads the tile count back)
-      }
-      if ((rc = snet_edge_tiles_packed(row_ptr, cut, N, ptile_e0 + ptile_k, ptile_nodes + 2 * ptile_k, (int64_t)cap - ptile_k, &nb, st)))
-        return rc;
-      ++m->eval_syncs;
-      pn_tiles = ptile_k + nb;
-      m->c_pn_tiles = pn_tiles;
-      m->c_ptile_k = ptile_k;
-    }
-  }
-  int32_t *center_t = nullptr, *w_row_t = nullptr;  // edges grouped by source (transposed scalar convolution)
-  float *sh_t = nullptr;
-  if (any_transposed && E > 0) {
-    if (m->topo_cache) {
-      if (m->c_edge_cap < (size_t)E + 64) {
-        if (m->c_center_t) (void)hipFree(m->c_center_t);
-        if (m->c_w_row_t) (void)hipFree(m->c_w_row_t);
-        m->c_center_t = m->c_w_row_t = nullptr;
-        m->c_edge_cap = (size_t)E + 64;
-        SNET_REQUIRE(hipMalloc((void **)&m->c_center_t, m->c_edge_cap * 4) == hipSuccess &&
-                         hipMalloc((void **)&m->c_w_row_t, m->c_edge_cap * 4) == hipSuccess, "snet_model_eval: alloc");
-      }
-      center_t = m->c_center_t;
-      w_row_t = m->c_w_row_t;
-    } else {
-      center_t = reinterpret_cast<int32_t *>(A.f((size_t)E + 64));
-      w_row_t = reinterpret_cast<int32_t *>(A.f((size_t)E + 64));
-    }
-    if (need_sh_t) sh_t = A.f((size_t)E * nsh + 64);
-    if (!topo_hit && (rc = snet_edges_by_source(row_ptr, N, eperm, pairs ? w_row : nullptr, E, center_t, w_row_t, st))) return rc;
-    if (need_sh_t && (rc = snet_gather_rows(sh, eperm, sh_t, E, nsh, st))) return rc;   // (the harmonics change with the positions: every step)
-  }
-  int32_t *tile_ptr_b = nullptr;   // boundary rows' tiles: tile_node + k, tile pointers re-based by -k
-  int64_t tile_k = 0;
-  if (hsplit && need_tiles[0]) {
-    if (m->c_tile_ptr_b_cap < (size_t)N + 64) {
-      if (m->c_tile_ptr_b) (void)hipFree(m->c_tile_ptr_b);
-      m->c_tile_ptr_b = nullptr;
-      m->c_tile_ptr_b_cap = (size_t)N + 64;
-      m->c_split_valid = false;
-      SNET_REQUIRE(hipMalloc((void **)&m->c_tile_ptr_b, m->c_tile_ptr_b_cap * 4) == hipSuccess, "snet_model_eval: alloc");
-    }
-    tile_ptr_b = m->c_tile_ptr_b;
-    if (topo_hit && m->c_split_valid) {
-      tile_k = m->c_tile_k;
-    } else {
-      int32_t k32 = 0;
-      SNET_REQUIRE(hipMemcpyAsync(&k32, tile_ptr + n_int, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                       hipStreamSynchronize(st) == hipSuccess, "snet_model_eval: tile readback failed");
-      ++m->eval_syncs;
-      tile_k = m->c_tile_k = k32;
-      if ((rc = snet_i32_shift(tile_ptr, -k32, tile_ptr_b, N + 1, st))) return rc;
-      m->c_split_valid = true;
-    }
-  }
-  if (!topo_hit && !(hsplit && need_tiles[0])) m->c_split_valid = false;   // a new graph was tiled without its boundary sub-list
-  if (m->topo_cache) {
-    m->topo_key = key;
-    m->topo_valid = true;
-  }
-  float *gw_buf[2] = {nullptr, nullptr};
-  bool gw_busy[2] = {false, false};
-  if (ov) {
-    gw_buf[0] = A.f((size_t)E * wn_max);
-    gw_buf[1] = A.f((size_t)E * wn_max);
+  if ((rc = topology(m, e))) return rc;
+  if (e.ov) {
+    e.gw_buf[0] = A.f((size_t)E * e.wn_max);
+    e.gw_buf[1] = A.f((size_t)E * e.wn_max);
     // every layer's radial weights depend on the edge embedding only: enqueue them all on the side stream now
     SNET_REQUIRE(hipEventRecord(m->ev_main, st) == hipSuccess && hipStreamWaitEvent(m->side, m->ev_main, 0) == hipSuccess,
                  "snet_model_eval: stream ordering failed");
     for (int t = 0; t < Lc; ++t) {
-      if ((rc = snet_radial_mlp_fwd(m->layers[t].mlp_plan, emb_w, WR, saved[t].w, m->side))) return rc;
+      if ((rc = snet_radial_mlp_fwd(m->layers[t].mlp_plan, e.emb_w, WR, e.saved[t].w, m->side))) return rc;
       SNET_REQUIRE(hipEventRecord(m->ev_w[t], m->side) == hipSuccess, "snet_model_eval: stream ordering failed");
     }
   }
-  const size_t mark = A.off;  // transient region starts here
+  e.mark = A.off;  // transient region starts here
 
-  {  // hidden activations of every fused layer's radial MLP in one launch (the layers share the edge embedding; up to 8 per call)
-    // (with their forward tangent h2': the reverse kernels take the radial gradient from it)
-    // first the layers whose reverse kernel runs in tangent mode, then the others: the order of engine.py)
-    const snet_mlp_plan *hp[8];
-    float *ho[8], *hd[8];
-    float *demb = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-      int nh = 0;
-      for (int t = 0; t <= Lc; ++t) {
-        if (t < Lc && m->layers[t].fused && (saved[t].wd != nullptr) == (pass == 0)) {
-          hp[nh] = m->layers[t].mlp_plan; ho[nh] = saved[t].w; hd[nh] = saved[t].wd; ++nh;
+  // hidden activations of every fused layer's radial MLP in one launch (the layers share the edge embedding; up to 8 per call)
+  // (with their forward tangent h2': the reverse kernels take the radial gradient from it)
+  // first the layers whose reverse kernel runs in tangent mode, then the others: the order of engine.py)
+  const snet_mlp_plan *hp[8];
+  float *ho[8], *hd[8];
+  float *demb = nullptr;
+  for (int pass = 0; pass < 2; ++pass) {
+    int nh = 0;
+    for (int t = 0; t <= Lc; ++t) {
+      if (t < Lc && m->layers[t].fused && (e.saved[t].wd != nullptr) == (pass == 0)) {
+        hp[nh] = m->layers[t].mlp_plan; ho[nh] = e.saved[t].w; hd[nh] = e.saved[t].wd; ++nh;
+      }
+      if (nh == 8 || (t == Lc && nh > 0)) {
+        if (pass == 0 && demb == nullptr) {
+          demb = A.f((size_t)WR * nb);
+          if ((rc = snet_edge_embed_tangent(&e.ep, m->coeffs.data(), e.edge_vec, pairs ? e.pair_edge : nullptr, WR, demb, st))) return rc;
         }
-        if (nh == 8 || (t == Lc && nh > 0)) {
-          if (pass == 0 && demb == nullptr) {
-            demb = A.f((size_t)WR * nb);
-            if ((rc = snet_edge_embed_tangent(&ep, m->coeffs.data(), edge_vec, pairs ? pair_edge : nullptr, WR, demb, st))) return rc;
-          }
-          if ((rc = pass == 0 ? snet_radial_mlp_hidden_fwd_layers_tangent(hp, nh, emb_w, demb, WR, ho, hd, st)
-                              : snet_radial_mlp_hidden_fwd_layers(hp, nh, emb_w, WR, ho, st))) return rc;
-          nh = 0;
-        }
+        if ((rc = pass == 0 ? snet_radial_mlp_hidden_fwd_layers_tangent(hp, nh, e.emb_w, demb, WR, ho, hd, st)
+                            : snet_radial_mlp_hidden_fwd_layers(hp, nh, e.emb_w, WR, ho, st))) return rc;
+        nh = 0;
       }
     }
   }
+  return 0;
+}
 
-  // ---------------- forward
-  for (int t = 0; t < Lc; ++t) {
+// ---- engine.py::_forward_layers
+int forward_layers(snet_model *m, Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E, WR = e.WR;
+  const int32_t *types = e.types, *row_ptr = e.row_ptr, *src = e.src, *w_row = e.pairs ? e.w_row : nullptr;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  int rc;
+  for (int t = 0; t < e.Lc; ++t) {
     Layer &L = m->layers[t];
-    A.off = mark;
+    const Saved &s = e.saved[t];
+    A.off = e.mark;
     float *sc = nullptr;
-    float *h = saved[t].h;
+    float *h = s.h;
     // the self-connection: its own launch (the rows SI2 then accumulates onto) only where the two-source launch after the
     // convolution does not apply
     const bool merged_y = t == 0 ? L.fwd_tab.ok : L.fwd2.ok;
     if (t == 0) {  // species-only inputs: table lookups (ghost rows included)
       if (L.sc.present() && !merged_y) {
-        sc = saved[t].y;
+        sc = s.y;
         if ((rc = snet_embed_rows(m->sc0_table, types, sc, N, L.gin, st))) return rc;
       }
       if ((rc = snet_embed_rows(m->h0_table, types, h, NT, L.dx, st))) return rc;
     } else {
       if (L.sc.present() && !merged_y) {
-        sc = saved[t].y;
-        if ((rc = run_linear(m, L.sc, x, sc, N, false, false, st))) return rc;
+        sc = s.y;
+        if ((rc = run_linear(m, L.sc, e.x, sc, N, false, false, st))) return rc;
       }
-      if ((rc = run_linear(m, L.si1, x, h, N, false, false, st))) return rc;
+      if ((rc = run_linear(m, L.si1, e.x, h, N, false, false, st))) return rc;
     }
-    const bool fsplit = hsplit && t > 0 && L.fused != nullptr;
-    if (t > 0 && has_halo) {
+    const bool fsplit = e.hsplit && t > 0 && L.fused != nullptr;
+    if (t > 0 && e.has_halo) {
       if (fsplit)  // the ghost rows travel on the halo stream while the hidden radial layers and the interior rows run
         SNET_REQUIRE(hipEventRecord(m->ev_h0, st) == hipSuccess && hipStreamWaitEvent(m->halo_stream, m->ev_h0, 0) == hipSuccess,
                      "snet_model_eval: stream ordering failed");
-      if ((rc = m->halo_fwd(m->halo_user, h, NT, N, L.dx, fsplit ? (void *)m->halo_stream : stream))) {
+      if ((rc = m->halo_fwd(m->halo_user, h, NT, N, L.dx, fsplit ? (void *)m->halo_stream : e.stream))) {
         snet::set_error("snet_model_eval: forward halo callback failed");
         return rc;
       }
@@ -1207,35 +1264,48 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         SNET_REQUIRE(hipMemset2DAsync(mid + z.first, (size_t)L.dmid * 4, 0, (size_t)z.second * 4, (size_t)N, st) == hipSuccess,
                      "snet_model_eval: memset");
     if (L.fused) {  // w = h2 @ W2 is formed inside the tensor-product kernel
-      const int64_t na = fsplit ? n_int : 0;   // rows [0, na) before the exchange has landed, [na, N) after
-      if (na > 0 && (rc = snet_conv_fwd_fused(L.fused, h, sh, saved[t].w, pairs ? w_row : nullptr, row_ptr, src, na, L.conv_scale, mid, st)))
+      const int64_t na = fsplit ? e.n_int : 0;   // rows [0, na) before the exchange has landed, [na, N) after
+      if (na > 0 && (rc = snet_conv_fwd_fused(L.fused, h, e.sh, s.w, w_row, row_ptr, src, na, L.conv_scale, mid, st)))
         return rc;
       if (fsplit) SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_h1, 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-      if ((rc = snet_conv_fwd_fused(L.fused, h, sh, saved[t].w, pairs ? w_row : nullptr, row_ptr + na, src, N - na, L.conv_scale,
+      if ((rc = snet_conv_fwd_fused(L.fused, h, e.sh, s.w, w_row, row_ptr + na, src, N - na, L.conv_scale,
                                     mid + (size_t)na * L.dmid, st)))
         return rc;
     } else {
-      if (ov)
+      if (e.ov)
         SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_w[t], 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-      else if ((rc = snet_radial_mlp_fwd(L.mlp_plan, emb_w, WR, saved[t].w, st)))
+      else if ((rc = snet_radial_mlp_fwd(L.mlp_plan, e.emb_w, WR, s.w, st)))
         return rc;
-      if ((rc = snet_conv_fwd(L.conv, h, sh, saved[t].w, pairs ? w_row : nullptr, row_ptr, src, N, L.conv_scale, mid, st)))
+      if ((rc = snet_conv_fwd(L.conv, h, e.sh, s.w, w_row, row_ptr, src, N, L.conv_scale, mid, st)))
         return rc;
     }
-    float *y = saved[t].y;   // (sc == y when the layer has a self-connection: SI2 accumulates into its rows, as engine.py does)
+    float *y = s.y;   // (sc == y when the layer has a self-connection: SI2 accumulates into its rows, as engine.py does)
     // -- or, the usual case, y = SI2(m) + sc(x) (layer 0: + the species table's row) written once by one launch per row list
     if (merged_y)
       rc = t == 0 ? run_multi(m, L.fwd_tab, mid, nullptr, y, N, m->sc0_table, types, st)
-                  : run_multi(m, L.fwd2, mid, x, y, N, nullptr, nullptr, st);
+                  : run_multi(m, L.fwd2, mid, e.x, y, N, nullptr, nullptr, st);
     else
       rc = run_linear(m, L.si2, mid, y, N, false, sc != nullptr, st);
     if (rc) return rc;
-    if ((rc = snet_gate_fwd(y, nullptr, x2, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(), st))) return rc;
-    std::swap(x, x2);
+    if ((rc = snet_gate_fwd(y, nullptr, e.x2, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(), st))) return rc;
+    std::swap(e.x, e.x2);
   }
-  A.off = mark;
-  float *ea = e_atom ? e_atom : A.f((size_t)N + 64);
-  float *g_x = x2, *gx_next = x;  // the forward features are dead after the readout: x / x2 ping-pong as gradient rows
+  return 0;
+}
+
+// ---- engine.py::_readout and _rescale_reduce: atomic energies and their sum, the seed of the reverse pass, the source-row bounds
+int readout(snet_model *m, Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E;
+  const int32_t *types = e.types;
+  const int Lc = e.Lc;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  int rc;
+  A.off = e.mark;
+  float *ea = e.e_atom ? e.e_atom : A.f((size_t)N + 64);
+  float *x = e.x;
+  float *g_x = e.g_x = e.x2;  // the forward features are dead after the readout: x / x2 ping-pong as gradient rows
+  e.gx_next = e.x;
   if (!m->fcn_dims.empty()) {
     // `readout_as_fcn`: the same launches, in the same order, as engine.py (exact fp32 GEMMs, activation kernels): bit-identical hosts
     const std::vector<int> &d = m->fcn_dims;
@@ -1253,7 +1323,7 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
         a = an;
       }
     }
-    if ((rc = snet_rescale_reduce(z, types, m->scale, m->shift, m->n_scale, N, ea, energy, st))) return rc;
+    if ((rc = snet_rescale_reduce(z, types, m->scale, m->shift, m->n_scale, N, ea, e.energy, st))) return rc;
     // reverse: dE/dz_last = scale[type]; then W^T and the activation's derivative per layer; the last product lands in g_x
     float *gz = A.f((size_t)N + 64);
     if ((rc = snet_readout_grad(m->one_d, 1, types, m->scale, m->n_scale, N, gz, st))) return rc;
@@ -1264,16 +1334,16 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       gz = ga;
     }
   } else {
-    if ((rc = snet_readout_energy(x, N, m->ro1.dim_in, m->ro_v, m->ro_c, types, m->scale, m->shift, m->n_scale, ea, energy, st)))
+    if ((rc = snet_readout_energy(x, N, m->ro1.dim_in, m->ro_v, m->ro_c, types, m->scale, m->shift, m->n_scale, ea, e.energy, st)))
       return rc;
-    // ---------------- reverse: dE/dx of the folded readout = scale[type] * v
+    // dE/dx of the folded readout = scale[type] * v
     if ((rc = snet_readout_grad(m->ro_v, m->ro1.dim_in, types, m->scale, m->n_scale, N, g_x, st))) return rc;
   }
-  SNET_REQUIRE(hipMemsetAsync(g_vec, 0, (size_t)E * 3 * 4, st) == hipSuccess &&
-                   (all_tangent || hipMemsetAsync(g_emb, 0, (size_t)E * nb * 4, st) == hipSuccess),
+  SNET_REQUIRE(hipMemsetAsync(e.g_vec, 0, (size_t)E * 3 * 4, st) == hipSuccess &&
+                   (e.all_tangent || hipMemsetAsync(e.g_emb, 0, (size_t)E * e.nb * 4, st) == hipSuccess),
                "snet_model_eval: memset failed");
   // fp16 operands of the fused reverse kernels: the source-row bounds of all layers from one launch (up to 8 matrices per call)
-  std::vector<float *> x_max_of((size_t)Lc, nullptr);
+  e.x_max_of.assign((size_t)Lc, nullptr);
   if (E > 0 && m->fused_terms == 4) {
     const float *xs[8];
     float *outs[8];
@@ -1281,10 +1351,10 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
     int32_t dims[8];
     int nj = 0;
     for (int t = 0; t <= Lc; ++t) {
-      if (t < Lc && m->layers[t].fused && !(t == 0 && l0 != nullptr) &&   // (snet_layer0_conv_bwd has no fp16 operand,
-          !(t == Lc - 1 && ll_on && m->layers[t].tfused && t > 0)) {      //  snet_lastlayer_conv_bwd none that depends on g_m)
-        x_max_of[t] = A.f((size_t)NT + 64);
-        xs[nj] = saved[t].h; outs[nj] = x_max_of[t]; rows[nj] = NT; dims[nj] = m->layers[t].dx; ++nj;
+      if (t < Lc && m->layers[t].fused && !(t == 0 && e.l0 != nullptr) &&   // (snet_layer0_conv_bwd has no fp16 operand,
+          !(t == Lc - 1 && e.ll_on && m->layers[t].tfused && t > 0)) {      //  snet_lastlayer_conv_bwd none that depends on g_m)
+        e.x_max_of[t] = A.f((size_t)NT + 64);
+        xs[nj] = e.saved[t].h; outs[nj] = e.x_max_of[t]; rows[nj] = NT; dims[nj] = m->layers[t].dx; ++nj;
       }
       if (nj == 8 || (t == Lc && nj > 0)) {
         if ((rc = snet_row_absmax_multi(xs, rows, dims, outs, nj, st))) return rc;
@@ -1292,147 +1362,211 @@ extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, 
       }
     }
   }
-  const size_t mark2 = A.off;
-  // g_x = sc^T g_y + SI1^T g_h once the ghost rows of g_h are complete: ONE two-source launch per row list that writes g_x, or --
-  // where that does not apply -- SI1^T g_h accumulated onto the rows sc^T g_y wrote before (in THIS order in every branch and in
-  // engine.py: the order is part of the result's last bits)
-  auto node_gx = [&](Layer &L, const float *g_y, const float *g_h, float *gx) -> int {
-    if (L.rev2.ok) return run_multi(m, L.rev2, g_y, g_h, gx, N, nullptr, nullptr, st);
-    return run_linear(m, L.si1, g_h, gx, N, true, L.sc.present(), st);
+  e.mark2 = A.off;
+  return 0;
+}
+
+// the reverse exchange of an un-split layer: ghost rows of g_h added onto their owners' rows (no halo installed: nothing)
+int halo_reverse(snet_model *m, Eval &e, float *g_h, int dx) {
+  if (!e.has_halo) return 0;
+  if (int rc = m->halo_rev(m->halo_user, g_h, e.NT, e.N, dx, e.stream)) {
+    snet::set_error("snet_model_eval: reverse halo callback failed");
+    return rc;
+  }
+  return 0;
+}
+
+// The end of a reverse layer t > 0: g_x (for the previous layer's gate output) = sc^T g_y + SI1^T g_h once the ghost rows of g_h are complete.
+// ONE two-source launch per row list that writes g_x, or -- where that does not apply -- sc^T g_y first, then SI1^T g_h accumulated onto its
+// rows: in THIS order, here and in engine.py.  An accumulating launch starts its accumulators from the rows already there, so the order is
+// part of the result's last bits.
+int finish_layer(snet_model *m, Eval &e, Layer &L, const float *g_y, float *g_h) {
+  const int64_t N = e.N;
+  hipStream_t st = e.st;
+  int rc;
+  if (L.sc.present() && !L.rev2.ok)   // (does not read the ghost gradients: as a launch of its own it runs under a split step's exchange)
+    if ((rc = run_linear(m, L.sc, g_y, e.gx_next, N, true, false, st))) return rc;
+  if (e.hsplit && L.fused) {   // a split step's exchange is still in flight
+    SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_h1, 0) == hipSuccess, "snet_model_eval: stream ordering failed");
+    if ((rc = snet_halo_reverse_accumulate(m->halo_user, g_h, L.dx, st))) return rc;
+  }
+  if ((rc = L.rev2.ok ? run_multi(m, L.rev2, g_y, g_h, e.gx_next, N, nullptr, nullptr, st)
+                      : run_linear(m, L.si1, g_h, e.gx_next, N, true, L.sc.present(), st)))
+    return rc;
+  std::swap(e.g_x, e.gx_next);
+  return 0;
+}
+
+// A fused layer: g_w is contracted inside the kernel, with w' = h2' W2 (tangent mode: the radial gradient lands in g_vec) or with W2^T -- and
+// with the hidden-layer tail not even g_h2 leaves it
+int reverse_layer_fused(snet_model *m, Eval &e, int t, const float *g_y, const float *g_m, float *g_xe, float *g_max, bool merged,
+                        bool transposed) {
+  const int64_t NT = e.NT, N = e.N, E = e.E;
+  const int32_t *types = e.types, *row_ptr = e.row_ptr, *src = e.src, *col_ptr = e.col_ptr, *eperm = e.eperm;
+  const int32_t *w_row = e.pairs ? e.w_row : nullptr;
+  const float *edge_vec = e.edge_vec;
+  float *sh = e.sh, *dsh = e.dsh, *g_vec = e.g_vec;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  Layer &L = m->layers[t];
+  const Saved &s = e.saved[t];
+  int rc;
+  const bool tg = s.wd != nullptr;
+  const bool tail = tg || snet_fused_plan_has_mlp_tail(L.fused) != 0;   // nothing of the radial branch left to reverse afterwards
+  float *g_h2 = tail ? nullptr : A.f((size_t)E * 64);
+  float *x_max = e.x_max_of[t];   // (bounds of every edge's g_w, see snet_row_absmax; computed before the layer loop)
+  auto bwd_tiles = [&](const int32_t *tp, const int32_t *tn, int64_t nt) -> int {
+    if (E <= 0 || nt <= 0 || merged) return 0;   // (merged: gh_rows adds to g_vec too)
+    if (tg)
+      return snet_conv_bwd_fused_tangent(L.fused, s.h, sh, dsh, s.w, s.wd, w_row, row_ptr, src,
+                                         tp, tn, nt, L.conv_scale, g_m, g_xe, edge_vec, g_vec, x_max, g_max, st);
+    return snet_conv_bwd_fused(L.fused, s.h, sh, dsh, s.w, w_row, row_ptr, src, tp, tn, nt,
+                               L.conv_scale, g_m, g_xe, g_h2, tail ? e.emb : nullptr, tail ? e.g_emb : nullptr, g_vec, x_max, g_max, st);
   };
-  for (int t = Lc - 1; t >= 0; --t) {
+  const bool rsplit = e.hsplit && t > 0;
+  const bool packed = L.tile_mode != 0;
+  auto bwd_all = [&]() -> int {
+    if (t == 0 && e.l0 != nullptr)   // transposed grouped GEMM per atom, then one pass over the edges: g_vec += spherical and radial part
+      return snet_layer0_conv_bwd(e.l0->plan, g_m, s.w, s.wd, w_row, row_ptr, src, types, e.l0->slot, sh,
+                                  dsh, edge_vec, N, A.f(e.l0_scratch), g_vec, st);
+    return packed ? bwd_tiles(e.ptile_e0, e.ptile_nodes, e.pn_tiles) : bwd_tiles(e.tile_ptr, e.tile_node, e.n_tiles);
+  };
+  if (!rsplit && (rc = bwd_all())) return rc;
+  float *g_h = nullptr;
+  if (t > 0) {
+    g_h = A.f((size_t)NT * L.dx);
+    // source rows [a, b) of g_h: the transposed scalar convolution over the edges grouped by source, or the segment sum
+    auto gh_rows = [&](int64_t a, int64_t b) -> int {
+      if (b <= a) return 0;
+      if (merged)
+        return snet_lastlayer_conv_bwd(L.merged, s.h, g_m, sh, dsh, edge_vec, s.w, s.wd, col_ptr, e.center_t,
+                                       e.w_row_t, eperm, a, b, L.conv_scale, g_h, g_vec, st);
+      if (transposed)
+        return snet_conv_fwd_fused(L.tfused, g_m, e.sh_t, s.w, e.w_row_t, col_ptr + a, e.center_t, b - a, L.conv_scale,
+                                   g_h + (size_t)a * L.dx, st);
+      return snet_segment_sum_rows_chunked(g_xe, col_ptr + a, eperm, b - a, L.dx, L.gxe_chunks, g_h + (size_t)a * L.dx, st);
+    };
+    if (transposed && !merged)
+      for (size_t i = 0; i + 1 < L.t_dead.size(); i += 2)
+        SNET_REQUIRE(hipMemset2DAsync(g_h + L.t_dead[i], (size_t)L.dx * 4, 0, (size_t)L.t_dead[i + 1] * 4, (size_t)NT, st) ==
+                         hipSuccess, "snet_model_eval: memset failed");
+    if (rsplit) {
+      // boundary tiles hold every edge with a ghost source: they go first, the ghost rows of g_h start travelling at once and
+      // the interior tiles / the local rows run under the exchange (the transposed convolution needs no tiles at all)
+      if (!transposed && (rc = packed ? bwd_tiles(e.ptile_e0 + e.ptile_k, e.ptile_nodes + 2 * e.ptile_k, e.pn_tiles - e.ptile_k)
+                                      : bwd_tiles(e.tile_ptr_b, e.tile_node + e.tile_k, e.n_tiles - e.tile_k))) return rc;
+      if ((rc = gh_rows(N, NT))) return rc;
+      SNET_REQUIRE(hipEventRecord(m->ev_h0, st) == hipSuccess && hipStreamWaitEvent(m->halo_stream, m->ev_h0, 0) == hipSuccess,
+                   "snet_model_eval: stream ordering failed");
+      if ((rc = snet_halo_reverse_exchange(m->halo_user, g_h, NT, N, L.dx, m->halo_stream))) return rc;
+      SNET_REQUIRE(hipEventRecord(m->ev_h1, m->halo_stream) == hipSuccess, "snet_model_eval: stream ordering failed");
+      if ((rc = transposed ? bwd_all() : packed ? bwd_tiles(e.ptile_e0, e.ptile_nodes, e.ptile_k) : bwd_tiles(e.tile_ptr, e.tile_node, e.tile_k)))
+        return rc;
+      if ((rc = gh_rows(0, N))) return rc;
+    } else {
+      if ((rc = gh_rows(0, NT))) return rc;
+      if ((rc = halo_reverse(m, e, g_h, L.dx))) return rc;
+    }
+  }
+  if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, e.emb, g_h2, E, e.g_emb, st))) return rc;
+  return t > 0 ? finish_layer(m, e, L, g_y, g_h) : 0;   // (layer-0 inputs depend on species only)
+}
+
+// A layer of separate kernels: the radial MLP's reverse pass reads g_w [E, wn], beside the rest of the reverse pass where a second stream is on
+int reverse_layer_separate(snet_model *m, Eval &e, int t, const float *g_y, const float *g_m, float *g_xe) {
+  const int64_t NT = e.NT, N = e.N, E = e.E;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  Layer &L = m->layers[t];
+  const Saved &s = e.saved[t];
+  int rc;
+  float *g_w = e.ov ? e.gw_buf[t & 1] : A.f((size_t)E * L.wn);
+  if (e.ov && e.gw_busy[t & 1])  // the MLP reverse of layer t+2 read this buffer on the side stream
+    SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_bwd[t & 1], 0) == hipSuccess, "snet_model_eval: stream ordering failed");
+  if ((rc = snet_conv_bwd_edge_vec(L.conv, s.h, e.sh, e.dsh, s.w, e.pairs ? e.w_row : nullptr, e.row_ptr, e.src, N,
+                                   L.conv_scale, g_m, g_w,
+                                   g_xe, e.g_vec, st)))
+    return rc;
+  if (e.ov) {  // only the final radial gradient needs g_emb: runs beside the rest of the reverse pass
+    SNET_REQUIRE(hipEventRecord(m->ev_main, st) == hipSuccess && hipStreamWaitEvent(m->side, m->ev_main, 0) == hipSuccess,
+                 "snet_model_eval: stream ordering failed");
+    if ((rc = snet_radial_mlp_bwd(L.mlp_plan, e.emb, g_w, E, e.g_emb, m->side))) return rc;
+    SNET_REQUIRE(hipEventRecord(m->ev_bwd[t & 1], m->side) == hipSuccess, "snet_model_eval: stream ordering failed");
+    e.gw_busy[t & 1] = true;
+  } else if ((rc = snet_radial_mlp_bwd(L.mlp_plan, e.emb, g_w, E, e.g_emb, st))) {
+    return rc;
+  }
+  if (t == 0) return 0;  // layer-0 inputs depend on species only
+  float *g_h = A.f((size_t)NT * L.dx);
+  if ((rc = snet_segment_sum_rows(g_xe, e.col_ptr, e.eperm, NT, L.dx, g_h, st))) return rc;
+  if ((rc = halo_reverse(m, e, g_h, L.dx))) return rc;
+  return finish_layer(m, e, L, g_y, g_h);
+}
+
+// ---- engine.py::_reverse_layers
+int reverse_layers(snet_model *m, Eval &e) {
+  const int64_t N = e.N, E = e.E;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  int rc;
+  for (int t = e.Lc - 1; t >= 0; --t) {
     Layer &L = m->layers[t];
-    A.off = mark2;
+    A.off = e.mark2;
     float *g_y = A.f((size_t)N * L.gin);
     // fp16 operands of the fused reverse kernel: bound of every row of g_m = SI2^T g_y (Cauchy-Schwarz), taken in the same pass
-    const bool merged = t > 0 && t == Lc - 1 && ll_on && L.tfused != nullptr && E > 0;
-    float *g_max = (L.fused && E > 0 && m->fused_terms == 4 && !(t == 0 && l0 != nullptr) && !merged) ? A.f((size_t)N) : nullptr;
-    if ((rc = snet_gate_bwd_norm(saved[t].y, g_x, g_y, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(),
+    const bool merged = t > 0 && t == e.Lc - 1 && e.ll_on && L.tfused != nullptr && E > 0;
+    float *g_max = (L.fused && E > 0 && m->fused_terms == 4 && !(t == 0 && e.l0 != nullptr) && !merged) ? A.f((size_t)N) : nullptr;
+    if ((rc = snet_gate_bwd_norm(e.saved[t].y, e.g_x, g_y, N, L.gin, L.dout, L.segs.data(), (int)L.segs.size(),
                                  g_max ? L.si2.t_norm : 0.f, g_max, st)))
       return rc;
     float *g_m = A.f((size_t)N * L.dmid);
     if ((rc = run_linear(m, L.si2, g_y, g_m, N, true, false, st))) return rc;
     const bool transposed = t > 0 && L.tfused != nullptr && E > 0;
     float *g_xe = t > 0 && !transposed ? A.f((size_t)E * L.dx) : nullptr;
-    if (L.fused) {  // g_w is contracted inside the kernel: with w' = h2' W2 (tangent mode: the radial gradient lands in g_vec), or with
-      // W2^T -- and with the hidden-layer tail not even g_h2 leaves it
-      const bool tg = saved[t].wd != nullptr;
-      const bool tail = tg || snet_fused_plan_has_mlp_tail(L.fused) != 0;   // nothing of the radial branch left to reverse afterwards
-      float *g_h2 = tail ? nullptr : A.f((size_t)E * 64);
-      float *x_max = x_max_of[t];   // (bounds of every edge's g_w, see snet_row_absmax; computed before the layer loop)
-      auto bwd_tiles = [&](const int32_t *tp, const int32_t *tn, int64_t nt) -> int {
-        if (E <= 0 || nt <= 0 || merged) return 0;   // (merged: gh_rows adds to g_vec too)
-        if (tg)
-          return snet_conv_bwd_fused_tangent(L.fused, saved[t].h, sh, dsh, saved[t].w, saved[t].wd, pairs ? w_row : nullptr, row_ptr, src,
-                                             tp, tn, nt, L.conv_scale, g_m, g_xe, edge_vec, g_vec, x_max, g_max, st);
-        return snet_conv_bwd_fused(L.fused, saved[t].h, sh, dsh, saved[t].w, pairs ? w_row : nullptr, row_ptr, src, tp, tn, nt,
-                                   L.conv_scale, g_m, g_xe, g_h2, tail ? emb : nullptr, tail ? g_emb : nullptr, g_vec, x_max, g_max, st);
-      };
-      const bool rsplit = hsplit && t > 0;
-      const bool packed = L.tile_mode != 0;
-      auto bwd_all = [&]() -> int {
-        if (t == 0 && l0 != nullptr)   // transposed grouped GEMM per atom, then one pass over the edges: g_vec += spherical and radial part
-          return snet_layer0_conv_bwd(l0->plan, g_m, saved[t].w, saved[t].wd, pairs ? w_row : nullptr, row_ptr, src, types, l0->slot, sh,
-                                      dsh, edge_vec, N, A.f(l0_scratch), g_vec, st);
-        return packed ? bwd_tiles(ptile_e0, ptile_nodes, pn_tiles) : bwd_tiles(tile_ptr, tile_node, n_tiles);
-      };
-      if (!rsplit && (rc = bwd_all())) return rc;
-      if (t > 0) {
-        float *g_h = A.f((size_t)NT * L.dx);
-        // source rows [a, b) of g_h: the transposed scalar convolution over the edges grouped by source, or the segment sum
-        auto gh_rows = [&](int64_t a, int64_t b) -> int {
-          if (b <= a) return 0;
-          if (merged)
-            return snet_lastlayer_conv_bwd(L.merged, saved[t].h, g_m, sh, dsh, edge_vec, saved[t].w, saved[t].wd, col_ptr, center_t,
-                                           w_row_t, eperm, a, b, L.conv_scale, g_h, g_vec, st);
-          if (transposed)
-            return snet_conv_fwd_fused(L.tfused, g_m, sh_t, saved[t].w, w_row_t, col_ptr + a, center_t, b - a, L.conv_scale,
-                                       g_h + (size_t)a * L.dx, st);
-          return snet_segment_sum_rows_chunked(g_xe, col_ptr + a, eperm, b - a, L.dx, L.gxe_chunks, g_h + (size_t)a * L.dx, st);
-        };
-        if (transposed && !merged)
-          for (size_t i = 0; i + 1 < L.t_dead.size(); i += 2)
-            SNET_REQUIRE(hipMemset2DAsync(g_h + L.t_dead[i], (size_t)L.dx * 4, 0, (size_t)L.t_dead[i + 1] * 4, (size_t)NT, st) ==
-                             hipSuccess, "snet_model_eval: memset failed");
-        if (rsplit) {
-          // boundary tiles hold every edge with a ghost source: they go first, the ghost rows of g_h start travelling at once and
-          // the interior tiles / the local rows run under the exchange (the transposed convolution needs no tiles at all)
-          if (!transposed && (rc = packed ? bwd_tiles(ptile_e0 + ptile_k, ptile_nodes + 2 * ptile_k, pn_tiles - ptile_k)
-                                          : bwd_tiles(tile_ptr_b, tile_node + tile_k, n_tiles - tile_k))) return rc;
-          if ((rc = gh_rows(N, NT))) return rc;
-          SNET_REQUIRE(hipEventRecord(m->ev_h0, st) == hipSuccess && hipStreamWaitEvent(m->halo_stream, m->ev_h0, 0) == hipSuccess,
-                       "snet_model_eval: stream ordering failed");
-          if ((rc = snet_halo_reverse_exchange(m->halo_user, g_h, NT, N, L.dx, m->halo_stream))) return rc;
-          SNET_REQUIRE(hipEventRecord(m->ev_h1, m->halo_stream) == hipSuccess, "snet_model_eval: stream ordering failed");
-          if ((rc = transposed ? bwd_all() : packed ? bwd_tiles(ptile_e0, ptile_nodes, ptile_k) : bwd_tiles(tile_ptr, tile_node, tile_k))) return rc;
-          if ((rc = gh_rows(0, N))) return rc;
-          if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, emb, g_h2, E, g_emb, st))) return rc;
-          if (L.sc.present() && !L.rev2.ok)   // sc^T g_y does not read the ghost gradients: as a launch of its own it runs under the exchange
-            if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
-          SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_h1, 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-          if ((rc = snet_halo_reverse_accumulate(m->halo_user, g_h, L.dx, st))) return rc;
-          if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
-          std::swap(g_x, gx_next);
-          continue;
-        }
-        if ((rc = gh_rows(0, NT))) return rc;
-        if (has_halo)
-          if ((rc = m->halo_rev(m->halo_user, g_h, NT, N, L.dx, stream))) {
-            snet::set_error("snet_model_eval: reverse halo callback failed");
-            return rc;
-          }
-        if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, emb, g_h2, E, g_emb, st))) return rc;
-        // g_x = sc^T g_y, then SI1^T g_h accumulated onto it -- in THIS order in every branch and in engine.py: an accumulating
-        // launch starts its accumulators from the rows already there, so the order is part of the result's last bits
-        if (L.sc.present() && !L.rev2.ok)
-          if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
-        if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
-        std::swap(g_x, gx_next);
-        continue;
-      }
-      if (!tail && (rc = snet_radial_mlp_hidden_bwd(L.mlp_plan, emb, g_h2, E, g_emb, st))) return rc;
-      break;  // layer-0 inputs depend on species only
-    }
-    float *g_w = ov ? gw_buf[t & 1] : A.f((size_t)E * L.wn);
-    if (ov && gw_busy[t & 1])  // the MLP reverse of layer t+2 read this buffer on the side stream
-      SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_bwd[t & 1], 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-    if ((rc = snet_conv_bwd_edge_vec(L.conv, saved[t].h, sh, dsh, saved[t].w, pairs ? w_row : nullptr, row_ptr, src, N,
-                                     L.conv_scale, g_m, g_w,
-                                     g_xe, g_vec, st)))
+    if ((rc = L.fused ? reverse_layer_fused(m, e, t, g_y, g_m, g_xe, g_max, merged, transposed) : reverse_layer_separate(m, e, t, g_y, g_m, g_xe)))
       return rc;
-    if (ov) {  // only the final radial gradient needs g_emb: runs beside the rest of the reverse pass
-      SNET_REQUIRE(hipEventRecord(m->ev_main, st) == hipSuccess && hipStreamWaitEvent(m->side, m->ev_main, 0) == hipSuccess,
-                   "snet_model_eval: stream ordering failed");
-      if ((rc = snet_radial_mlp_bwd(L.mlp_plan, emb, g_w, E, g_emb, m->side))) return rc;
-      SNET_REQUIRE(hipEventRecord(m->ev_bwd[t & 1], m->side) == hipSuccess, "snet_model_eval: stream ordering failed");
-      gw_busy[t & 1] = true;
-    } else if ((rc = snet_radial_mlp_bwd(L.mlp_plan, emb, g_w, E, g_emb, st))) {
-      return rc;
-    }
-    if (t == 0) break;  // layer-0 inputs depend on species only
-    float *g_h = A.f((size_t)NT * L.dx);
-    if ((rc = snet_segment_sum_rows(g_xe, col_ptr, eperm, NT, L.dx, g_h, st))) return rc;
-    if (has_halo)
-      if ((rc = m->halo_rev(m->halo_user, g_h, NT, N, L.dx, stream))) {
-        snet::set_error("snet_model_eval: reverse halo callback failed");
-        return rc;
-      }
-    // g_x (for the previous layer's gate output) = sc^T g_y + SI1^T g_h (same order as above)
-    if (L.sc.present() && !L.rev2.ok)
-      if ((rc = run_linear(m, L.sc, g_y, gx_next, N, true, false, st))) return rc;
-    if ((rc = node_gx(L, g_y, g_h, gx_next))) return rc;
-    std::swap(g_x, gx_next);
   }
   for (int b = 0; b < 2; ++b)
-    if (gw_busy[b])
+    if (e.gw_busy[b])
       SNET_REQUIRE(hipStreamWaitEvent(st, m->ev_bwd[b], 0) == hipSuccess, "snet_model_eval: stream ordering failed");
-  if (!all_tangent && (rc = snet_edge_embed_bwd(&ep, m->coeffs.data(), edge_vec, E, g_emb, nullptr, g_vec, 1, st))) return rc;
-  A.off = mark2;
-  float *F = forces ? forces : A.f((size_t)NT * 3);
-  if ((rc = snet_edge_force(g_vec, edge_vec, row_ptr, col_ptr, eperm, NT, E, F, virial_atom, virial, st))) return rc;
-  if (has_halo && m->fold_forces) {
-    if ((rc = m->halo_rev(m->halo_user, F, NT, N, 3, stream))) return rc;
-    if (virial_atom && (rc = m->halo_rev(m->halo_user, virial_atom, NT, N, 6, stream))) return rc;
+  return 0;
+}
+
+// ---- engine.py::_forces
+int forces(snet_model *m, Eval &e) {
+  const int64_t NT = e.NT, N = e.N, E = e.E;
+  hipStream_t st = e.st;
+  Arena &A = m->arena;
+  int rc;
+  if (!e.all_tangent && (rc = snet_edge_embed_bwd(&e.ep, m->coeffs.data(), e.edge_vec, E, e.g_emb, nullptr, e.g_vec, 1, st))) return rc;
+  A.off = e.mark2;
+  float *F = e.forces ? e.forces : A.f((size_t)NT * 3);
+  if ((rc = snet_edge_force(e.g_vec, e.edge_vec, e.row_ptr, e.col_ptr, e.eperm, NT, E, F, e.virial_atom, e.virial, st))) return rc;
+  if (e.has_halo && m->fold_forces) {
+    if ((rc = m->halo_rev(m->halo_user, F, NT, N, 3, e.stream))) return rc;
+    if (e.virial_atom && (rc = m->halo_rev(m->halo_user, e.virial_atom, NT, N, 6, e.stream))) return rc;
   }
   return 0;
 }
+}  // namespace
+
+extern "C" int64_t snet_model_eval_syncs(const snet_model *m) { return m ? m->eval_syncs : -1; }
+
+// One energy + force evaluation: the phases of engine.py's `compute`, in its order, over one Eval
+extern "C" int snet_model_eval(snet_model *m, int64_t NT, int64_t N, int64_t E, const int32_t *types,
+                               const int32_t *types_host, const int32_t *row_ptr, const int32_t *src,
+                               const int32_t *col_ptr, const int32_t *eperm, const float *edge_vec,
+                               const int32_t *w_row, const int32_t *pair_edge, int64_t n_pairs, double *energy,
+                               float *e_atom, float *dE_dr, float *forces, double *virial, float *virial_atom,
+                               void *stream) {
+  SNET_REQUIRE(m != nullptr, "snet_model_eval: null model");
+  Eval e{NT, N, E, types, types_host, row_ptr, src, col_ptr, eperm, edge_vec, w_row, pair_edge, n_pairs,
+         energy, e_atom, dE_dr, forces, virial, virial_atom, stream};
+  int rc;
+  if ((rc = begin(m, e))) return rc;
+  if ((rc = forward_layers(m, e))) return rc;
+  if ((rc = readout(m, e))) return rc;
+  if ((rc = reverse_layers(m, e))) return rc;
+  return ::forces(m, e);   // (the phase, not the argument of the same name)
+}
+

@@ -247,3 +247,26 @@ def test_engine_functions_stay_reviewable():
     tree = ast.parse(open(path).read())
     long = [(n.name, n.end_lineno - n.lineno + 1) for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.end_lineno - n.lineno + 1 > 200]
     assert long == []
+
+
+def test_native_sequencer_functions_stay_reviewable():
+    """the native host has the Python host's shape: snet_model_eval (one 583-line function before) runs the phases begin,
+    forward_layers, readout, reverse_layers, forces, named after engine.py's methods, and nothing in snet_model.cpp is over the 200
+    lines engine.py is held to.  A function: from a definition head (test_stream_discipline_cpu._HEAD) to the next `}` in column 0"""
+    import ast
+    import os
+    from test_stream_discipline_cpu import _HEAD
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'sevennet_amd')
+    lines = open(os.path.join(pkg, 'csrc', 'snet_model.cpp')).read().split('\n')
+    length = {}
+    for k, line in enumerate(lines):
+        m = _HEAD.match(line)
+        if m and not line.rstrip().endswith(';'):
+            end = next(j for j in range(k, len(lines)) if lines[j].startswith('}'))
+            length[m.group(1)] = max(length.get(m.group(1), 0), end - k + 1)
+    assert {'snet_model_eval', 'snet_model_load_memory', 'plan_multi_source', 'layer0_select'} <= set(length)   # the scan finds definitions
+    assert length['snet_model_load_memory'] > 150                                                             # ... and their ends
+    assert [(n, v) for n, v in length.items() if v > 200] == []
+    assert {'begin', 'forward_layers', 'readout', 'reverse_layers', 'forces'} <= set(length)
+    methods = {n.name for n in ast.walk(ast.parse(open(os.path.join(pkg, 'engine.py')).read())) if isinstance(n, ast.FunctionDef)}
+    assert {'_begin', '_forward_layers', '_readout', '_reverse_layers', '_forces'} <= methods

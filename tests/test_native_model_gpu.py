@@ -84,6 +84,27 @@ def test_native_model_vs_engine_and_oracle(case):
     _assert_identical(a, nat.compute(g, want_atomic_virial=True))
 
 
+def test_native_model_one_stream_unfused(monkeypatch):
+    """SNET_NO_OVERLAP=1, read when a model is loaded: the separate radial-MLP kernels of the unfused path on the caller's stream, in
+    the layer loops.  Same bits as the default two-stream model and as the Python host on one stream"""
+    from sevennet_amd.engine import HipForceEngine, build_graph
+    from sevennet_amd.native_model import NativeModel
+    from sevennet_amd.shapes import unit_test_config
+    from sevennet_amd.synthetic import random_state_dict
+    cfg = unit_test_config()
+    sd = random_state_dict(cfg, seed=7)
+    types, pos, cell, ei, ev = synthetic_system((2, 2, 2), sigma=0.08, seed=11, cutoff=4.0, n_species=4)
+    monkeypatch.setenv('SNET_NO_OVERLAP', '1')
+    one = NativeModel(cfg, sd, device='cuda:0')
+    monkeypatch.delenv('SNET_NO_OVERLAP')
+    two = NativeModel(cfg, sd, device='cuda:0')
+    eng = HipForceEngine(cfg, sd, device='cuda:0', overlap=False)
+    g = build_graph(types, ei, ev, device='cuda:0', num_species=eng.spec.num_species)
+    a = one.compute(g, want_atomic_virial=True)
+    _assert_identical(two.compute(g, want_atomic_virial=True), a)
+    _assert_identical(eng.compute(g, want_atomic_virial=True), a)
+
+
 def test_native_model_isolated_atom_and_errors(tmp_path):
     from sevennet_amd import _lib
     from sevennet_amd.engine import build_graph
