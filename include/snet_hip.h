@@ -540,6 +540,19 @@ int snet_fire_step(double *pos, double *vel, const float *forces, const double *
                    const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos, int32_t *active,
                    int32_t *n_steps, double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max,
                    int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step, void *stream);
+/* snet_fire_step_fixed: the same step with components held fixed.  hold (device int32 [n_atoms], not NULL): bit k (k = 0, 1, 2) of
+ * hold[i] & 7 says that Cartesian component k of atom i is held, so 7 holds the whole atom (the name keeps it apart from the 0/1
+ * `fixed` array of snet_neb_forces).  For a held component (i, k): its force is taken as 0 by selection, not by multiplication -- a
+ * non-finite force there poisons nothing -- and that 0 is what enters every sum of the step (max |F_i|^2, F.v, |F|^2, |v|^2,
+ * |dt v|^2); its velocity is taken as 0 whatever vel holds on entry and is stored as 0 by a step that moves; pos[3 i + k] is never
+ * written.  So fmax_sys and convergence refer to the free components only, and a system whose components are all held is found
+ * converged (fm = 0 < fmax) on the first launch with no step counted.  With hold all zero every output equals snet_fire_step's bit
+ * for bit.  The arrival word is the one of snet_fire_step: calls of the two on one device follow each other in stream order.  */
+int snet_fire_step_fixed(double *pos, double *vel, const float *forces, const double *forces_extra, int64_t n_atoms,
+                         const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos, int32_t *active,
+                         int32_t *n_steps, double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max,
+                         int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step,
+                         const int32_t *hold, void *stream);
 
 /* ---- batched variable-cell FIRE relaxation step (unit masses) -----------------------------------
  * One step of FIRE over the atoms AND the cell of n_sys systems in ONE launch: the rule of ASE's UnitCellFilter (Tadmor et al.,
@@ -572,6 +585,20 @@ int snet_fire_cell_step(double *pos, double *vel, double *cell, double *vel_cell
                         double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step,
                         double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain, int32_t constant_volume,
                         double min_height, void *stream);
+/* snet_fire_cell_step_fixed: the same step with whole atoms held.  hold as for snet_fire_step_fixed, read per atom: an atom with
+ * hold[i] & 7 != 0 is held (a rule per component has no clean form under a sheared F; the Python driver refuses such masks).  Its
+ * force counts as 0: g_i = 0 in every sum, by selection on g_i = f_i F (a non-finite force there poisons nothing, and a free atom's
+ * g_i is formed exactly as without a mask); its reference-frame velocity is taken as 0 and stored as 0.  Its position still goes through r_i = (r_i F^-T) F_new^T: a held atom keeps its fractional
+ * coordinates and moves with the cell, which is what ASE's UnitCellFilter does with FixAtoms.  The virial and the cell force are
+ * untouched, and the n of G /= n and F_new = F + dQ / n stays the system's full atom count (ASE: len(atoms)).  With hold all zero
+ * every output equals snet_fire_cell_step's bit for bit; the arrival word is the one of snet_fire_cell_step.  */
+int snet_fire_cell_step_fixed(double *pos, double *vel, double *cell, double *vel_cell, const double *cell0, const float *forces,
+                              const double *forces_extra, const double *virial, const double *virial_extra, int64_t n_atoms,
+                              const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos, int32_t *active,
+                              int32_t *n_steps, int32_t *status, double *fmax_sys, int32_t *n_active, double fmax, double dt_start,
+                              double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha,
+                              double max_step, double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain,
+                              int32_t constant_volume, double min_height, const int32_t *hold, void *stream);
 
 /* ---- batched nudged-elastic-band forces ----------------------------------------------------------
  * The NEB forces of the moving images of n_bands bands in ONE launch: the improved tangent of Henkelman and Jonsson, J. Chem.
@@ -793,6 +820,22 @@ int snet_mdb_step(double *pos, double *vel, const float *forces, const double *f
                   double *e_kin, double dt, double c1, double c2, uint64_t seed, int32_t phase, void *stream);
 int snet_mdb_init_velocities(double *vel, const double *mass, int64_t n_atoms, const int32_t *seg_ptr, const int32_t *sys_id,
                              int32_t n_sys, const double *kT, uint64_t seed, int32_t remove_com, void *stream);
+/* snet_mdb_step_fixed: the same step with components held fixed (hold as for snet_fire_step_fixed, not NULL).  A held component
+ * (i, k) gets no kick, no drift and no thermostat noise: pos[3 i + k] is not written, vel[3 i + k] is stored as 0 (by every phase
+ * that stores velocities) and the component contributes 0 to e_kin.  The noise counters do not depend on the mask -- a free
+ * component draws exactly what it draws without one -- and every update of the step is component-wise, so the free components
+ * equal snet_mdb_step's on the same inputs bit for bit.  snet_mdb_npt_step has no masked form.
+ *
+ * snet_mdb_init_velocities_fixed: held components are 0.  A system with no held component is treated exactly as by
+ * snet_mdb_init_velocities, bit for bit.  For a system with at least one: the centre-of-mass shift is skipped (the held atoms
+ * anchor the frame), and with remove_com != 0 the velocities are scaled so that the kinetic energy is (1/2) dof kT[s] exactly,
+ * dof = 3 n_s - (held components); with dof = 0 all velocities are 0 (no 0/0).                                                  */
+int snet_mdb_step_fixed(double *pos, double *vel, const float *forces, const double *forces_extra, const double *mass, int64_t n_atoms,
+                        const int32_t *seg_ptr, const int32_t *sys_id, int32_t n_sys, const double *kT, int32_t *step_index,
+                        double *e_kin, double dt, double c1, double c2, uint64_t seed, int32_t phase, const int32_t *hold, void *stream);
+int snet_mdb_init_velocities_fixed(double *vel, const double *mass, int64_t n_atoms, const int32_t *seg_ptr, const int32_t *sys_id,
+                                   int32_t n_sys, const double *kT, uint64_t seed, int32_t remove_com, const int32_t *hold,
+                                   void *stream);
 
 /* ---- batched isotropic NPT MD step (the cell moves on the device) --------------------------------
  * snet_mdb_step with the stochastic cell rescaling of Bernetti and Bussi, J. Chem. Phys. 153, 114107 (2020), isotropic form: a

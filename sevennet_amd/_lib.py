@@ -161,6 +161,13 @@ SIGNATURES = {
                                       c_f64p, c_f64p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_double, c_stream]),
+    'snet_fire_step_fixed': (C.c_int, [c_f64p, c_f64p, c_f32p, c_f64p, C.c_int64, c_i32p, C.c_int32, c_f64p, c_f64p, c_i32p, c_i32p,
+                                       c_i32p, c_f64p, c_i32p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, c_i32p, c_stream]),
+    'snet_fire_cell_step_fixed': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p,
+                                            C.c_int32, c_f64p, c_f64p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p, C.c_double,
+                                            C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_i32p, c_stream]),
     'snet_neb_forces': (C.c_int, [c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, C.c_int32, c_i32p, C.c_int32, c_f64p, c_i32p,
                                   C.c_int64, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p, c_f64p, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p,
                                   c_stream]),
@@ -187,6 +194,10 @@ SIGNATURES = {
                                 C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int32, c_stream]),
     'snet_mdb_init_velocities': (C.c_int, [c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, C.c_uint64, C.c_int32,
                                            c_stream]),
+    'snet_mdb_step_fixed': (C.c_int, [c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, c_i32p, c_f64p,
+                                      C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int32, c_i32p, c_stream]),
+    'snet_mdb_init_velocities_fixed': (C.c_int, [c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32, c_f64p, C.c_uint64, C.c_int32,
+                                                 c_i32p, c_stream]),
     'snet_mdb_npt_step': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32,
                                     c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p, C.c_double, C.c_double,
                                     C.c_double, C.c_uint64, C.c_int32, C.c_double, C.c_double, c_stream]),

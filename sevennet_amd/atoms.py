@@ -6,6 +6,8 @@ from typing import Any, Dict, List
 
 import numpy as np
 
+from .fixed import constraints_fixed_list
+
 try:  # ASE is optional: without it the calculators are plain objects that expose compute() and the batched surfaces
     from ase.calculators.calculator import Calculator, all_changes
     HAVE_ASE = True
@@ -47,6 +49,16 @@ def atoms_velocities(atoms_list, kw: dict) -> dict:
     return dict(kw, velocities=[np.asarray(v, np.float64) for v in vels])
 
 
+def atoms_fixed(atoms_list, kw: dict) -> dict:
+    """the keyword arguments of relax_many / md_many for ASE-like objects: `fixed_list` from the objects' `constraints` (FixAtoms,
+    FixCartesian; fixed.constraints_fixed_list) when the caller passed none and some object holds something.  Objects without
+    constraints leave kw as it is; a constraint of another kind raises ValueError."""
+    if kw.get('fixed_list') is not None:
+        return kw
+    fixed_list = constraints_fixed_list(atoms_list)
+    return kw if fixed_list is None else dict(kw, fixed_list=fixed_list)
+
+
 class ManyAtomsMixin:
     """`calculate_many`, `relax_many_atoms`, `neb_many_atoms`, `vibrations_many_atoms`, `phonons_many_atoms`, `elastic_many_atoms` and
     `md_many_atoms` over ASE-like objects, for a class that has `compute_many`, `relax_many`, `neb_many`, `vibrations_many`,
@@ -59,8 +71,11 @@ class ManyAtomsMixin:
     def relax_many_atoms(self, atoms_list, fmax: float = 0.05, steps: int = 500, **kw) -> List[Dict[str, Any]]:
         """`relax_many` over ASE-like objects (get_atomic_numbers / get_positions / get_cell / get_pbc / set_positions): the
         relaxed positions are written back with `set_positions`; with relax_cell=True the relaxed cell first, with
-        `set_cell(cell, scale_atoms=False)`"""
+        `set_cell(cell, scale_atoms=False)`.  Without a `fixed_list` of the caller's the objects' `constraints` are read:
+        FixAtoms and FixCartesian become the `fixed_list` of `relax_many`, any other constraint raises ValueError (it is not
+        dropped: the object would end up in a state no calculation produced)."""
         atoms_list = list(atoms_list)
+        kw = atoms_fixed(atoms_list, kw)
         results = self.relax_many(*atoms_args(atoms_list), fmax=fmax, steps=steps, **kw)
         for a, r in zip(atoms_list, results):
             if kw.get('relax_cell'):
@@ -110,8 +125,10 @@ class ManyAtomsMixin:
         A sqrt(amu / eV) = 10.1805 fs, so the velocities of a real ase.Atoms are in A / (10.1805 fs): multiply
         get_velocities() by ase.units.fs (0.0982269) on the way in and divide by it on the way out, or pass
         `velocities=` in A/fs yourself (it takes precedence over the objects').  Because the mistake would be silent, objects of
-        the ase package are refused (ValueError) unless `velocities=` is passed."""
+        the ase package are refused (ValueError) unless `velocities=` is passed.  Without a `fixed_list` of the caller's the
+        objects' `constraints` are read as in `relax_many_atoms`."""
         atoms_list = list(atoms_list)
+        kw = atoms_fixed(atoms_list, kw)
         numbers, positions, cells, pbcs = atoms_args(atoms_list)
         results = self.md_many(numbers, positions, [a.get_masses() for a in atoms_list], cells, pbcs, dt, steps,
                                **atoms_velocities(atoms_list, kw))

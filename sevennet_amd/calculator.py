@@ -299,7 +299,11 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         batch when enough have finished.  One dict per system, in the given order: the keys of `compute` (evaluated at the
         returned positions) plus `positions` [n,3] fp64, `converged` (largest atomic force below fmax, eV/A) and `n_steps`.
         A system that is not converged after `steps` steps is returned with converged = False.  kw: repack_below, extra (as
-        relax_batch) and the FIRE parameters (relax.FIRE_DEFAULTS).  The call's counters are kept as `self.relax_info`."""
+        relax_batch) and the FIRE parameters (relax.FIRE_DEFAULTS).  The call's counters are kept as `self.relax_info`.
+        fixed_list: per system None, a bool mask [n] or an index list of atoms, or a bool mask [n,3] of Cartesian components that
+        do not move (with relax_cell whole atoms only, which keep their fractional coordinates); their `positions` come back
+        with the caller's bits, `converged` refers to the free components, `forces` stay the true forces, and the dicts gain
+        `fixed` [n,3] (relax_batch)."""
         from .relax import relax_batch
         if len(numbers_list) != len(positions_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays but {len(positions_list)} position arrays')
@@ -414,7 +418,10 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         the GPU too: further kw compressibility (A^3/eV, required), barostat_time (fs, default 1000) and max_log_volume_step
         (default 0.1); every system fully periodic with at most batch.BATCH_MAX_ATOMS atoms.  The dicts then gain `cell` [3,3]
         (the keys of `compute` are those at the returned positions AND cell), `volume` and `pressure` over the logged steps and
-        `status`: 'ok' or 'cell_failed' (md_batch)."""
+        `status`: 'ok' or 'cell_failed' (md_batch).
+        fixed_list: per system None, a bool mask [n] or an index list of atoms, or a bool mask [n,3] of Cartesian components that
+        do not move: no kick, no drift, no noise, velocity 0 (held components of `velocities` are set to 0), `temperature`
+        over the remaining degrees of freedom; the dicts gain `fixed` [n,3].  Not together with pressure= (md_batch)."""
         from .md import md_batch
         if not len(numbers_list) == len(positions_list) == len(masses_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '

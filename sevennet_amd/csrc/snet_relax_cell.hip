@@ -22,10 +22,31 @@ struct FireCellParams {
   int mask_bits, hydrostatic, constant_volume;
 };
 
+// the force g = f F and the velocity v of atom i in the reference frame, F the deformation gradient; HOLD: both are 0, by selection,
+// for an atom with a bit of its mask set (whole atoms only), so that it keeps its coordinates in the reference frame.  The
+// selection stands behind the product: a free atom's g is formed from the same operands, in the same text, as without a mask.
+template <bool HOLD>
+__device__ __forceinline__ void load_atom(const float *__restrict__ forces, const double *__restrict__ forces_extra,
+                                          const double *__restrict__ vel, const int32_t *__restrict__ hold, int64_t i,
+                                          const double *F, double (&g)[3], double (&v)[3]) {
+  double f[3];
+  load_force(forces, forces_extra, i, f);
+  row_mul(f, F, g);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v[k] = vel[3 * i + k];
+  if constexpr (HOLD) {
+    const int h = held_bits(hold, i) != 0 ? 7 : 0;
+    zero_held(h, g);
+    zero_held(h, v);
+  }
+}
+
+// HOLD = false (snet_fire_cell_step) never reads `hold`
+template <bool HOLD>
 __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(
     double *__restrict__ pos, double *__restrict__ vel, double *__restrict__ cell, double *__restrict__ vel_cell,
     const double *__restrict__ cell0, const float *__restrict__ forces, const double *__restrict__ forces_extra,
-    const double *__restrict__ virial, const double *__restrict__ virial_extra, int64_t n, const int32_t *__restrict__ seg_ptr,
+    const int32_t *__restrict__ hold, const double *__restrict__ virial, const double *__restrict__ virial_extra, int64_t n, const int32_t *__restrict__ seg_ptr,
     int n_sys, double *__restrict__ dt_s, double *__restrict__ alpha_s, int32_t *__restrict__ n_pos_s, int32_t *__restrict__ active_s,
     int32_t *__restrict__ n_steps_s, int32_t *__restrict__ status_s, double *__restrict__ fmax_sys, int32_t *__restrict__ n_active,
     FireCellParams p) {
@@ -83,10 +104,9 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(
     double f2max = 0.0;
     double acc[3] = {0.0, 0.0, 0.0};
     for (int64_t i = a0 + tid; i < a1; i += FIRE_THREADS) {
-      double f[3], g[3];
-      load_force(forces, forces_extra, i, f);
-      row_mul(f, F, g);
-      const double vx = vel[3 * i + 0], vy = vel[3 * i + 1], vz = vel[3 * i + 2];
+      double g[3], v[3];
+      load_atom<HOLD>(forces, forces_extra, vel, hold, i, F, g, v);
+      const double vx = v[0], vy = v[1], vz = v[2];
       const double f2 = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];
       f2max = max_nan(f2, f2max);
       acc[0] += g[0] * vx + g[1] * vy + g[2] * vz;
@@ -119,12 +139,11 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(
       // pass 2: |dt v|^2 of the new velocities, which are not stored yet
       double d2[1] = {0.0};
       for (int64_t i = a0 + tid; i < a1; i += FIRE_THREADS) {
-        double f[3], g[3];
-        load_force(forces, forces_extra, i, f);
-        row_mul(f, F, g);
+        double g[3], v[3];
+        load_atom<HOLD>(forces, forces_extra, vel, hold, i, F, g, v);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const double dr = dt * new_velocity(vel[3 * i + k], g[k], keep, push, nF, nV, dt);
+          const double dr = dt * new_velocity(v[k], g[k], keep, push, nF, nV, dt);
           d2[0] += dr * dr;
         }
       }
@@ -173,15 +192,14 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(
         }
         // pass 3: the velocities (the values of pass 2 again) and the move  r = (r F^-T + dq) F_new^T
         for (int64_t i = a0 + tid; i < a1; i += FIRE_THREADS) {
-          double f[3], g[3], r[3], q[3];
-          load_force(forces, forces_extra, i, f);
-          row_mul(f, F, g);
+          double g[3], r[3], q[3], v0[3];
+          load_atom<HOLD>(forces, forces_extra, vel, hold, i, F, g, v0);
 #pragma unroll
           for (int k = 0; k < 3; ++k) r[k] = pos[3 * i + k];
           row_mul_t(r, Finv, q);
 #pragma unroll
           for (int k = 0; k < 3; ++k) {
-            const double v = new_velocity(vel[3 * i + k], g[k], keep, push, nF, nV, dt);
+            const double v = new_velocity(v0[k], g[k], keep, push, nF, nV, dt);
             vel[3 * i + k] = v;
             double dq = dt * v;
             if (clip) dq = dq * scale;
@@ -197,6 +215,33 @@ __global__ __launch_bounds__(FIRE_THREADS) void fire_cell_step_kernel(
   if (tid == 0) count_active(&g_fire_cell_arrivals, still_active, n_sys, n_active);
 }
 
+template <bool HOLD>
+int fire_cell_step_launch(const char *name, double *pos, double *vel, double *cell, double *vel_cell, const double *cell0,
+                          const float *forces, const double *forces_extra, const double *virial, const double *virial_extra,
+                          int64_t n_atoms, const int32_t *seg_ptr, int32_t n_sys, double *dt, double *alpha, int32_t *n_pos,
+                          int32_t *active, int32_t *n_steps, int32_t *status, double *fmax_sys, int32_t *n_active, double fmax,
+                          double dt_start, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha_start, double f_alpha,
+                          double max_step, double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain,
+                          int32_t constant_volume, double min_height, const int32_t *hold, void *stream) {
+  SNET_REQUIRE(n_sys >= 1 && n_atoms >= 0 && n_atoms < (1ll << 31), std::string(name) + ": bad shape");
+  SNET_REQUIRE(pos && vel && cell && vel_cell && cell0 && forces && virial && seg_ptr && dt && alpha && n_pos && active && n_steps &&
+                   status && fmax_sys && n_active && (hold || !HOLD),
+               std::string(name) + ": null argument");
+  FireCellParams p;
+  p.fire = FireParams{fmax, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step, n_min};
+  SNET_REQUIRE(fire_params_ok(fmax, dt_start, p.fire), std::string(name) + ": FIRE parameters out of range");
+  SNET_REQUIRE(scalar_pressure - scalar_pressure == 0.0 && cell_mask_bits >= 0 && cell_mask_bits < 64 && min_height >= 0 &&
+                   !(hydrostatic_strain && constant_volume),
+               std::string(name) + ": cell parameters out of range");
+  p.pressure = scalar_pressure, p.min_height = min_height, p.mask_bits = cell_mask_bits;
+  p.hydrostatic = hydrostatic_strain != 0, p.constant_volume = constant_volume != 0;
+  fire_cell_step_kernel<HOLD><<<(unsigned)n_sys, FIRE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+      pos, vel, cell, vel_cell, cell0, forces, forces_extra, hold, virial, virial_extra, n_atoms, seg_ptr, n_sys, dt, alpha, n_pos,
+      active, n_steps, status, fmax_sys, n_active, p);
+  SNET_CHECK_LAUNCH(name);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int snet_fire_cell_step(double *pos, double *vel, double *cell, double *vel_cell, const double *cell0, const float *forces,
@@ -206,21 +251,22 @@ extern "C" int snet_fire_cell_step(double *pos, double *vel, double *cell, doubl
                                    double dt_start, double dt_max, int32_t n_min, double f_inc, double f_dec, double alpha_start,
                                    double f_alpha, double max_step, double scalar_pressure, int32_t cell_mask_bits,
                                    int32_t hydrostatic_strain, int32_t constant_volume, double min_height, void *stream) {
-  SNET_REQUIRE(n_sys >= 1 && n_atoms >= 0 && n_atoms < (1ll << 31), "snet_fire_cell_step: bad shape");
-  SNET_REQUIRE(pos && vel && cell && vel_cell && cell0 && forces && virial && seg_ptr && dt && alpha && n_pos && active && n_steps &&
-                   status && fmax_sys && n_active,
-               "snet_fire_cell_step: null argument");
-  FireCellParams p;
-  p.fire = FireParams{fmax, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step, n_min};
-  SNET_REQUIRE(fire_params_ok(fmax, dt_start, p.fire), "snet_fire_cell_step: FIRE parameters out of range");
-  SNET_REQUIRE(scalar_pressure - scalar_pressure == 0.0 && cell_mask_bits >= 0 && cell_mask_bits < 64 && min_height >= 0 &&
-                   !(hydrostatic_strain && constant_volume),
-               "snet_fire_cell_step: cell parameters out of range");
-  p.pressure = scalar_pressure, p.min_height = min_height, p.mask_bits = cell_mask_bits;
-  p.hydrostatic = hydrostatic_strain != 0, p.constant_volume = constant_volume != 0;
-  fire_cell_step_kernel<<<(unsigned)n_sys, FIRE_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
-      pos, vel, cell, vel_cell, cell0, forces, forces_extra, virial, virial_extra, n_atoms, seg_ptr, n_sys, dt, alpha, n_pos, active,
-      n_steps, status, fmax_sys, n_active, p);
-  SNET_CHECK_LAUNCH("snet_fire_cell_step");
-  return 0;
+  return fire_cell_step_launch<false>("snet_fire_cell_step", pos, vel, cell, vel_cell, cell0, forces, forces_extra, virial, virial_extra,
+                                      n_atoms, seg_ptr, n_sys, dt, alpha, n_pos, active, n_steps, status, fmax_sys, n_active, fmax,
+                                      dt_start, dt_max, n_min, f_inc, f_dec, alpha_start, f_alpha, max_step, scalar_pressure,
+                                      cell_mask_bits, hydrostatic_strain, constant_volume, min_height, nullptr, stream);
+}
+
+extern "C" int snet_fire_cell_step_fixed(double *pos, double *vel, double *cell, double *vel_cell, const double *cell0,
+                                         const float *forces, const double *forces_extra, const double *virial,
+                                         const double *virial_extra, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_sys, double *dt,
+                                         double *alpha, int32_t *n_pos, int32_t *active, int32_t *n_steps, int32_t *status,
+                                         double *fmax_sys, int32_t *n_active, double fmax, double dt_start, double dt_max, int32_t n_min,
+                                         double f_inc, double f_dec, double alpha_start, double f_alpha, double max_step,
+                                         double scalar_pressure, int32_t cell_mask_bits, int32_t hydrostatic_strain,
+                                         int32_t constant_volume, double min_height, const int32_t *hold, void *stream) {
+  return fire_cell_step_launch<true>("snet_fire_cell_step_fixed", pos, vel, cell, vel_cell, cell0, forces, forces_extra, virial,
+                                     virial_extra, n_atoms, seg_ptr, n_sys, dt, alpha, n_pos, active, n_steps, status, fmax_sys, n_active,
+                                     fmax, dt_start, dt_max, n_min, f_inc, f_dec, alpha_start, f_alpha, max_step, scalar_pressure,
+                                     cell_mask_bits, hydrostatic_strain, constant_volume, min_height, hold, stream);
 }

@@ -175,6 +175,20 @@ __device__ __forceinline__ void load_force(const float *__restrict__ forces, con
     for (int k = 0; k < 3; ++k) F[k] += forces_extra[3 * i + k];
   }
 }
+// the hold mask of the *_fixed entry points: bit k of hold[i] & 7 says that Cartesian component k of atom i is held
+__device__ __forceinline__ int held_bits(const int32_t *__restrict__ hold, int64_t i) { return hold[i] & 7; }
+__device__ __forceinline__ bool is_held(int h, int k) { return ((h >> k) & 1) != 0; }
+// x with its held components replaced by 0, by selection: what a held component carried (a NaN force, a stale velocity) goes nowhere
+__device__ __forceinline__ void zero_held(int h, double (&x)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) x[k] = is_held(h, k) ? 0.0 : x[k];
+}
+// load_force under a mask
+__device__ __forceinline__ void load_force_free(const float *__restrict__ forces, const double *__restrict__ forces_extra, int64_t i,
+                                                int h, double (&F)[3]) {
+  load_force(forces, forces_extra, i, F);
+  zero_held(h, F);
+}
 
 // FIRE (snet_fire_step, snet_fire_cell_step)
 struct FireParams {
@@ -240,14 +254,21 @@ struct BaoabStep {
   uint32_t sys, step;
 };
 // one atom (i, number `a` of its system) through the step; returns m |v|^2 after the finishing kick.  Nothing is stored where
-// neither phase bit is set.
+// neither phase bit is set.  HOLD (snet_mdb_step_fixed): the components in the mask bits h enter with velocity and force 0, so
+// that they are neither kicked nor counted in m |v|^2; their positions are not written and their velocities are stored as 0.
+// The noise is drawn as without a mask, and every update is component-wise: a free component sees the arithmetic of HOLD = false.
+template <bool HOLD = false>
 __device__ __forceinline__ double baoab_atom(const BaoabStep &p, double *__restrict__ pos, double *__restrict__ vel,
                                              const float *__restrict__ forces, const double *__restrict__ forces_extra,
-                                             const double *__restrict__ mass, int64_t i, uint32_t a) {
+                                             const double *__restrict__ mass, int64_t i, uint32_t a, int h = 0) {
   const double m = mass[i];
   double v[3] = {vel[3 * i + 0], vel[3 * i + 1], vel[3 * i + 2]};
   double F[3] = {0.0, 0.0, 0.0};
   if (p.finish || p.start) load_force(forces, forces_extra, i, F);
+  if constexpr (HOLD) {
+    zero_held(h, v);
+    zero_held(h, F);
+  }
   if (p.finish) half_kick3(v, F, p.half_kick, m);
   const double mv2 = m * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
   if (p.start) {
@@ -272,10 +293,17 @@ __device__ __forceinline__ double baoab_atom(const BaoabStep &p, double *__restr
         x[k] += 0.5 * p.dt * v[k];
       }
     }
+    if constexpr (HOLD) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) pos[3 * i + k] = x[k];
+      for (int k = 0; k < 3; ++k)
+        if (!is_held(h, k)) pos[3 * i + k] = x[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) pos[3 * i + k] = x[k];
+    }
   }
   if (p.finish || p.start) {
+    if constexpr (HOLD) zero_held(h, v);   // (the thermostat's noise on a held component goes nowhere)
 #pragma unroll
     for (int k = 0; k < 3; ++k) vel[3 * i + k] = v[k];
   }

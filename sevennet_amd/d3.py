@@ -402,7 +402,9 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         under model + D3 (systems periodic along all three axes, at most batch.BATCH_MAX_ATOMS atoms, as for the model alone).
         The plan leaves each system's lattice sums room for one more repetition per axis than its starting cell needs; a cell
         that shrinks beyond that makes the D3 virial NaN, which the step kernel refuses: the system comes back as it was
-        before that step with status 'cell_failed'."""
+        before that step with status 'cell_failed'.
+        fixed_list (SevenNetCalculator.relax_many) goes through with either d3_term: the masked step ignores the model's and the
+        D3 forces alike on held components, and the summed `forces` of the results stay the true ones."""
         self._check_d3_term(d3_term)
         if kw.get('relax_cell') and d3_term == 'host':
             raise ValueError("relax_cell is not available with d3_term='host': that D3 term reaches the optimizer through the `extra` "
@@ -535,7 +537,9 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         `compute_many` at the returned positions.
         pressure= (constant-pressure MD, SevenNetCalculator.md_many) needs d3_term='device', whose term carries a virial: the D3
         virial then enters the barostat's pressure, and the D3 share of the results is evaluated at the returned cells.  With
-        'host' it raises ValueError."""
+        'host' it raises ValueError.
+        fixed_list (SevenNetCalculator.md_many) goes through with either d3_term: held components feel neither the model's nor the
+        D3 forces."""
         self._check_d3_term(d3_term)
         npt = kw.get('pressure') is not None
         if npt and d3_term == 'host':

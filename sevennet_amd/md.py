@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from .batch import _MAX_IMAGE_REACH, BatchForces, _as_host, batch_results, system_of, validate_batch_inputs
+from .fixed import attach_fixed, held_components, hold_masks
 from .relax import check_cell_relax_systems
 
 ACC = 9.648533212e-3    # eV / (A amu) in A / fs^2
@@ -121,34 +122,47 @@ def validate_md_inputs(masses, n_at: np.ndarray, dt, steps, temperature, frictio
 
 def md_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor,
             sys_id: torch.Tensor, kT: torch.Tensor, step_index: torch.Tensor, e_kin: torch.Tensor, dt: float, c1: float, c2: float,
-            seed: int, phase: int, forces_extra: Optional[torch.Tensor] = None) -> None:
+            seed: int, phase: int, forces_extra: Optional[torch.Tensor] = None, hold: Optional[torch.Tensor] = None) -> None:
     """one `snet_mdb_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C ABI:
-    pos / vel / mass / kT / e_kin fp64, forces fp32, forces_extra fp64, seg_ptr / sys_id / step_index int32)"""
+    pos / vel / mass / kT / e_kin fp64, forces fp32, forces_extra fp64, seg_ptr / sys_id / step_index int32).  hold (int32 [N],
+    bit k of a word: component k of that atom is held; fixed.hold_masks): the launch is `snet_mdb_step_fixed`."""
     N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
     want = [(pos, torch.float64, (N, 3)), (vel, torch.float64, (N, 3)), (forces, torch.float32, (N, 3)), (mass, torch.float64, (N,)),
             (seg_ptr, torch.int32, (B + 1,)), (sys_id, torch.int32, (B,)), (kT, torch.float64, (B,)), (step_index, torch.int32, (B,)),
             (e_kin, torch.float64, (B,))]
     if forces_extra is not None:
         want.append((forces_extra, torch.float64, (N, 3)))
+    if hold is not None:
+        want.append((hold, torch.int32, (N,)))
     _lib.check_device_tensors('md_step', pos, want)
     P = _lib.ptr
+    args = (P(pos), P(vel), P(forces), P(forces_extra), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), P(step_index), P(e_kin),
+            float(dt), float(c1), float(c2), int(seed), int(phase))
     with torch.cuda.device(pos.device):
-        _lib.check(_lib.load().snet_mdb_step(
-            P(pos), P(vel), P(forces), P(forces_extra), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), P(step_index), P(e_kin),
-            float(dt), float(c1), float(c2), int(seed), int(phase), _lib.stream()), 'snet_mdb_step')
+        if hold is None:
+            _lib.check(_lib.load().snet_mdb_step(*args, _lib.stream()), 'snet_mdb_step')
+        else:
+            _lib.check(_lib.load().snet_mdb_step_fixed(*args, P(hold), _lib.stream()), 'snet_mdb_step_fixed')
 
 
 def init_velocities(vel: torch.Tensor, mass: torch.Tensor, seg_ptr: torch.Tensor, sys_id: torch.Tensor, kT: torch.Tensor,
-                    seed: int, remove_com: bool = True) -> None:
-    """one `snet_mdb_init_velocities` launch on the current stream: Maxwell-Boltzmann velocities at kT (eV) into vel"""
+                    seed: int, remove_com: bool = True, hold: Optional[torch.Tensor] = None) -> None:
+    """one `snet_mdb_init_velocities` launch on the current stream: Maxwell-Boltzmann velocities at kT (eV) into vel.  hold (int32
+    [N], as `md_step`): the launch is `snet_mdb_init_velocities_fixed` -- held components are 0, and a system with some is not
+    shifted to its centre of mass but scaled (remove_com) to a kinetic energy of (3 n - held components) kT / 2."""
     N, B = int(vel.shape[0]), int(seg_ptr.numel()) - 1
-    _lib.check_device_tensors('init_velocities', vel, [(vel, torch.float64, (N, 3)), (mass, torch.float64, (N,)),
-                                                       (seg_ptr, torch.int32, (B + 1,)), (sys_id, torch.int32, (B,)),
-                                                       (kT, torch.float64, (B,))])
+    want = [(vel, torch.float64, (N, 3)), (mass, torch.float64, (N,)), (seg_ptr, torch.int32, (B + 1,)), (sys_id, torch.int32, (B,)),
+            (kT, torch.float64, (B,))]
+    if hold is not None:
+        want.append((hold, torch.int32, (N,)))
+    _lib.check_device_tensors('init_velocities', vel, want)
     P = _lib.ptr
+    args = (P(vel), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), int(seed), int(bool(remove_com)))
     with torch.cuda.device(vel.device):
-        _lib.check(_lib.load().snet_mdb_init_velocities(P(vel), P(mass), N, P(seg_ptr), P(sys_id), B, P(kT), int(seed),
-                                                        int(bool(remove_com)), _lib.stream()), 'snet_mdb_init_velocities')
+        if hold is None:
+            _lib.check(_lib.load().snet_mdb_init_velocities(*args, _lib.stream()), 'snet_mdb_init_velocities')
+        else:
+            _lib.check(_lib.load().snet_mdb_init_velocities_fixed(*args, P(hold), _lib.stream()), 'snet_mdb_init_velocities_fixed')
 
 
 def _per_system(x, B: int, what: str, unit: str) -> np.ndarray:
@@ -228,10 +242,11 @@ def md_npt_step(pos: torch.Tensor, vel: torch.Tensor, cell: torch.Tensor, forces
 
 def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray, *,
             dt: float, steps: int, friction: float, seed: int, log_every: int, traj_every: int, remove_com: bool,
-            want_atomic_virial: bool):
+            want_atomic_virial: bool, hold: Optional[np.ndarray] = None):
     """The MD loop over the force call `forces` (a BatchForces on validated inputs; `validate_md_inputs`) -> (graph and engine
     output of the last force call, dict of device tensors: pos, vel [N,3], e_pot, e_kin [samples,B], traj [frames,N,3] or None,
-    step_index [B]; info)"""
+    step_index [B]; info).  hold (int32 [N] on the host, fixed.hold_masks, or None): the components held fixed; the held
+    components of vel0 are taken as 0."""
     dev = forces.engine.dev
     n_atoms = forces.n_atoms
     B, steps, log_every, traj_every = len(n_atoms), int(steps), int(log_every), int(traj_every)
@@ -242,11 +257,12 @@ def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.
                else up(positions, np.float64)).reshape(-1, 3).clone()
         N = int(pos.shape[0])
         m_d, kT_d, id_d, seg = up(mass, np.float64), up(kT, np.float64), up(ids, np.int32), up(forces.a_ptr, np.int32)
+        hold_d = None if hold is None else up(hold, np.int32)
         if vel0 is None:
             vel = torch.empty_like(pos)
-            init_velocities(vel, m_d, seg, id_d, kT_d, seed, remove_com)
+            init_velocities(vel, m_d, seg, id_d, kT_d, seed, remove_com, hold_d)
         else:
-            vel = up(vel0, np.float64)
+            vel = up(vel0 if hold is None else np.where(held_components(hold), 0.0, vel0), np.float64)
         step_index = torch.zeros(B, dtype=torch.int32, device=dev)
         e_kin = torch.zeros(B, dtype=torch.float64, device=dev)
         e_pot_log = torch.zeros(steps // log_every + 1, B, dtype=torch.float64, device=dev)
@@ -259,7 +275,7 @@ def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.
             if traj is not None and k % traj_every == 0:
                 traj[k // traj_every].copy_(pos)   # x_k: the launch below moves on to x_{k+1}
             md_step(pos, vel, out['forces'], m_d, seg, id_d, kT_d, step_index, e_kin, dt, c1, c2, seed,
-                    (FINISH if k > 0 else 0) | (0 if last else START), fx)
+                    (FINISH if k > 0 else 0) | (0 if last else START), fx, hold_d)
             if k % log_every == 0:   # e_kin is the kinetic energy of v_k, the potential energy that of x_k
                 j = k // log_every
                 e_pot_log[j].copy_(out['energy_per_system'] if ex is None else out['energy_per_system'] + ex)
@@ -320,9 +336,11 @@ def md_npt_loop(forces: BatchForces, positions, cells, mass: np.ndarray, vel0: O
     return g, out, state, info
 
 
-def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms) -> List[Dict[str, Any]]:
+def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms, hold: Optional[np.ndarray] = None) -> List[Dict[str, Any]]:
     """`positions`, `velocities`, `e_pot`, `e_kin`, `temperature` (and `trajectory`) into each system's results dict: the one
-    transfer to the host"""
+    transfer to the host.  hold (int32 [N], fixed.hold_masks): a system with held components has 3 n - (held components) degrees
+    of freedom in `temperature`, and 0.0 K where none is left"""
+    n_held = None if hold is None else held_components(hold).sum(1)
     pos_h, vel_h = state['pos'].cpu().numpy(), state['vel'].cpu().numpy()
     e_pot, e_kin = state['e_pot'].cpu().numpy(), state['e_kin'].cpu().numpy()
     traj = None if state['traj'] is None else state['traj'].cpu().numpy()
@@ -331,6 +349,10 @@ def attach_md(results: List[Dict[str, Any]], state: dict, seg_ptr_host, n_atoms)
         res['positions'], res['velocities'] = pos_h[a0:a1].copy(), vel_h[a0:a1].copy()
         res['e_pot'], res['e_kin'] = e_pot[:, b].copy(), e_kin[:, b].copy()
         res['temperature'] = 2.0 * res['e_kin'] / (3.0 * int(n_atoms[b]) * KB)
+        held = 0 if n_held is None else int(n_held[a0:a1].sum())
+        if held:
+            dof = 3 * int(n_atoms[b]) - held
+            res['temperature'] = 2.0 * res['e_kin'] / (dof * KB) if dof else np.zeros_like(res['e_kin'])
         if traj is not None:
             res['trajectory'] = traj[:, a0:a1].copy()
     return results
@@ -351,7 +373,7 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
              friction: float = 0.0, velocities=None, seed: int = 0, log_every: int = 1, traj_every: int = 0, remove_com: bool = True,
              extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
              system_ids=None, pressure=None, compressibility=None, barostat_time: float = 1000.0,
-             max_log_volume_step: float = 0.1) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+             max_log_volume_step: float = 0.1, fixed_list=None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
     """`steps` MD steps of `dt` fs for B structures: NVE (friction 0) or Langevin at `temperature` at fixed cells, or with
     `pressure` isotropic NPT, the cells moving on the device.
 
@@ -387,12 +409,28 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     results gain `cell` [3,3] fp64 (energy, forces and stress are those at the returned positions AND cell), `volume` (A^3) and
     `pressure` (eV/A^3) over the logged steps, and `status`: 'ok', or 'cell_failed' where the step kernel refused a next cell
     (de not finite -- a NaN virial --, |de| > max_log_volume_step, or a height below cutoff / 64): that system is returned as it
-    was before that step and stays in the batch, measured and not moved."""
+    was before that step and stays in the batch, measured and not moved.
+
+    fixed_list: the atoms and Cartesian components that do not move: per system None, a bool mask [n] or an integer index list of
+    whole atoms, or a bool mask [n,3] of components (fixed.hold_masks).  The step kernel (snet_mdb_step_fixed) gives a held
+    component no kick, no drift and no thermostat noise: its position keeps the caller's bits, its velocity is 0 and it adds
+    nothing to `e_kin`; the free components see the arithmetic and the noise they see without a mask.  Held components of
+    caller-supplied `velocities` are set to 0 (as ASE's set_momenta does under a constraint).  Drawn velocities: a system with
+    held components is not shifted to its centre of mass -- the held atoms anchor the frame -- and with remove_com its kinetic
+    energy is dof kT / 2 exactly, dof = 3 n - (held components), which is also the dof of its `temperature` (0.0 K where dof = 0);
+    a system with nothing held keeps 3 n.  `forces` stay the model's true forces, on held atoms too.  Together with `pressure`
+    fixed_list raises ValueError: constant-pressure MD with frozen atoms is not a defined ensemble here.  When something is held
+    the results gain `fixed`, a bool array [n,3]; with fixed_list None, or masks that hold nothing, the call is the one without
+    the argument: the same launches, the same dicts."""
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
     mass, vel0, kT, ids = validate_md_inputs(masses, n_at, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
                                              system_ids)
+    hold = hold_masks(fixed_list, n_at)
     if pressure is not None:
+        if fixed_list is not None:
+            raise ValueError('fixed_list with pressure: constant-pressure MD with atoms held fixed is not a defined ensemble here '
+                             '(the barostat rescales every position); run at fixed cells, or without fixed_list')
         p0, beta_over_tau = validate_npt_inputs(n_at, cells, pbcs, cutoff, pressure, compressibility, barostat_time,
                                                 max_log_volume_step, extra)
         forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
@@ -406,6 +444,6 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
     g, out, state, info = md_loop(forces, positions, mass, vel0, kT, ids, dt=dt, steps=steps, friction=friction, seed=seed,
                                   log_every=log_every, traj_every=traj_every, remove_com=remove_com,
-                                  want_atomic_virial=want_atomic_virial)
-    results = batch_results(g, out, cells, want_atomic_virial)
-    return attach_md(results, state, g.seg_ptr_host, n_at), info
+                                  want_atomic_virial=want_atomic_virial, hold=hold)
+    results = attach_md(batch_results(g, out, cells, want_atomic_virial), state, g.seg_ptr_host, n_at, hold)
+    return (results if hold is None else attach_fixed(results, hold, g.seg_ptr_host)), info

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from .batch import _MAX_IMAGE_REACH, BatchForces, batch_results, classify_systems, device_positions, validate_batch_inputs
+from .fixed import attach_fixed, check_whole_atoms, hold_masks
 
 STATUS_NAMES = ('steps', 'converged', 'cell_failed')   # by the status word of snet_fire_cell_step (0: still running at the step cap)
 FIRE_DEFAULTS = dict(dt_start=0.1, dt_max=1.0, n_min=5, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, max_step=0.2)
@@ -139,33 +140,43 @@ class RepackBook:
 
 def fire_step(pos: torch.Tensor, vel: torch.Tensor, forces: torch.Tensor, seg_ptr: torch.Tensor, dt: torch.Tensor,
               alpha: torch.Tensor, n_pos: torch.Tensor, active: torch.Tensor, n_steps: torch.Tensor, fmax_sys: torch.Tensor,
-              n_active: torch.Tensor, fmax: float, params: dict, forces_extra: Optional[torch.Tensor] = None) -> None:
+              n_active: torch.Tensor, fmax: float, params: dict, forces_extra: Optional[torch.Tensor] = None,
+              hold: Optional[torch.Tensor] = None) -> None:
     """one `snet_fire_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C ABI:
-    pos / vel / dt / alpha / fmax_sys fp64, forces fp32, forces_extra fp64, the rest int32)"""
+    pos / vel / dt / alpha / fmax_sys fp64, forces fp32, forces_extra fp64, the rest int32).  hold (int32 [N], bit k of a word:
+    component k of that atom is held; fixed.hold_masks): the launch is `snet_fire_step_fixed`."""
     N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
     want = [(pos, torch.float64, (N, 3)), (vel, torch.float64, (N, 3)), (forces, torch.float32, (N, 3)), (seg_ptr, torch.int32, (B + 1,)),
             (dt, torch.float64, (B,)), (alpha, torch.float64, (B,)), (n_pos, torch.int32, (B,)), (active, torch.int32, (B,)),
             (n_steps, torch.int32, (B,)), (fmax_sys, torch.float64, (B,)), (n_active, torch.int32, (1,))]
     if forces_extra is not None:
         want.append((forces_extra, torch.float64, (N, 3)))
+    if hold is not None:
+        want.append((hold, torch.int32, (N,)))
     _lib.check_device_tensors('fire_step', pos, want)
     P = _lib.ptr
-    with torch.cuda.device(pos.device):
-        _lib.check(_lib.load().snet_fire_step(
-            P(pos), P(vel), P(forces), P(forces_extra), N, P(seg_ptr), B, P(dt), P(alpha), P(n_pos), P(active), P(n_steps),
+    args = (P(pos), P(vel), P(forces), P(forces_extra), N, P(seg_ptr), B, P(dt), P(alpha), P(n_pos), P(active), P(n_steps),
             P(fmax_sys), P(n_active), float(fmax), params['dt_start'], params['dt_max'], params['n_min'], params['f_inc'],
-            params['f_dec'], params['alpha_start'], params['f_alpha'], params['max_step'], _lib.stream()), 'snet_fire_step')
+            params['f_dec'], params['alpha_start'], params['f_alpha'], params['max_step'])
+    with torch.cuda.device(pos.device):
+        if hold is None:
+            _lib.check(_lib.load().snet_fire_step(*args, _lib.stream()), 'snet_fire_step')
+        else:
+            _lib.check(_lib.load().snet_fire_step_fixed(*args, P(hold), _lib.stream()), 'snet_fire_step_fixed')
 
 
-def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack_below: float, params: dict):
+def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack_below: float, params: dict,
+              hold: Optional[np.ndarray] = None):
     """The relaxation loop over the force call `forces` (a BatchForces on validated inputs; `check_fire_params`): -> (positions
-    fp64 [N,3] on the device in the caller's order, n_steps [B], converged [B], info)"""
+    fp64 [N,3] on the device in the caller's order, n_steps [B], converged [B], info).  hold (int32 [N] on the host,
+    fixed.hold_masks, or None): the components held fixed; the mask goes to the device once and is regathered at a repack."""
     dev = forces.engine.dev
     book = RepackBook(forces.n_atoms)
     B = book.B
     with torch.cuda.device(dev):
         pos = device_positions(positions, dev).clone()
         vel = torch.zeros_like(pos)
+        hold = None if hold is None else torch.as_tensor(np.ascontiguousarray(hold, np.int32)).to(dev)
         dt = torch.full((B,), float(params['dt_start']), dtype=torch.float64, device=dev)
         alpha = torch.full((B,), float(params['alpha_start']), dtype=torch.float64, device=dev)
         n_pos = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -176,7 +187,8 @@ def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack
         fire_launches = 0
         for _ in range(int(steps)):
             g, out, fx = forces(pos, book.ids)[:3]   # (FIRE has no use for the extra energies)
-            fire_step(pos, vel, out['forces'], g.seg_ptr, dt, alpha, n_pos, active, n_steps, fmax_sys, n_active, fmax, params, fx)
+            fire_step(pos, vel, out['forces'], g.seg_ptr, dt, alpha, n_pos, active, n_steps, fmax_sys, n_active, fmax, params, fx,
+                      hold)
             fire_launches += 1
             left = int(n_active.item())   # the one readback of the step
             if left == 0:
@@ -186,6 +198,7 @@ def fire_loop(forces: BatchForces, positions, *, fmax: float, steps: int, repack
                 keep, rows = book.repack(pos, act_h, st_h)
                 rows_d, keep_d = torch.as_tensor(rows).to(dev), torch.as_tensor(keep).to(dev)
                 pos, vel = pos[rows_d], vel[rows_d]   # (gathers copy: the stored slices keep the old buffer)
+                hold = None if hold is None else hold[rows_d]
                 dt, alpha, n_pos, active, n_steps, fmax_sys = (t[keep_d] for t in (dt, alpha, n_pos, active, n_steps, fmax_sys))
         act_h, st_h = torch.stack([active, n_steps]).cpu().numpy()
         book.store(pos, act_h, st_h, only_finished=False)
@@ -199,10 +212,12 @@ def fire_cell_step(pos: torch.Tensor, vel: torch.Tensor, cell: torch.Tensor, vel
                    forces: torch.Tensor, virial: torch.Tensor, seg_ptr: torch.Tensor, dt: torch.Tensor, alpha: torch.Tensor,
                    n_pos: torch.Tensor, active: torch.Tensor, n_steps: torch.Tensor, status: torch.Tensor, fmax_sys: torch.Tensor,
                    n_active: torch.Tensor, fmax: float, params: dict, cell_params: dict, min_height: float,
-                   forces_extra: Optional[torch.Tensor] = None, virial_extra: Optional[torch.Tensor] = None) -> None:
+                   forces_extra: Optional[torch.Tensor] = None, virial_extra: Optional[torch.Tensor] = None,
+                   hold: Optional[torch.Tensor] = None) -> None:
     """one `snet_fire_cell_step` launch on the current stream; every tensor on the device, updated in place (dtypes as the C
     ABI: pos / vel / cell / vel_cell / cell0 / virial / virial_extra / forces_extra / dt / alpha / fmax_sys fp64, forces fp32, the
-    rest int32).  params: `check_fire_params`; cell_params: `check_cell_params`."""
+    rest int32).  params: `check_fire_params`; cell_params: `check_cell_params`.  hold (int32 [N], a nonzero word: that atom is
+    held; fixed.hold_masks): the launch is `snet_fire_cell_step_fixed`."""
     N, B = int(pos.shape[0]), int(seg_ptr.numel()) - 1
     f64, i32 = torch.float64, torch.int32
     want = [(pos, f64, (N, 3)), (vel, f64, (N, 3)), (cell, f64, (B, 9)), (vel_cell, f64, (B, 9)), (cell0, f64, (B, 9)),
@@ -213,26 +228,32 @@ def fire_cell_step(pos: torch.Tensor, vel: torch.Tensor, cell: torch.Tensor, vel
         want.append((forces_extra, f64, (N, 3)))
     if virial_extra is not None:
         want.append((virial_extra, f64, (B, 6)))
+    if hold is not None:
+        want.append((hold, i32, (N,)))
     _lib.check_device_tensors('fire_cell_step', pos, want)
     P = _lib.ptr
-    with torch.cuda.device(pos.device):
-        _lib.check(_lib.load().snet_fire_cell_step(
-            P(pos), P(vel), P(cell), P(vel_cell), P(cell0), P(forces), P(forces_extra), P(virial), P(virial_extra), N, P(seg_ptr), B,
+    args = (P(pos), P(vel), P(cell), P(vel_cell), P(cell0), P(forces), P(forces_extra), P(virial), P(virial_extra), N, P(seg_ptr), B,
             P(dt), P(alpha), P(n_pos), P(active), P(n_steps), P(status), P(fmax_sys), P(n_active), float(fmax), params['dt_start'],
             params['dt_max'], params['n_min'], params['f_inc'], params['f_dec'], params['alpha_start'], params['f_alpha'],
             params['max_step'], cell_params['scalar_pressure'], cell_params['cell_mask_bits'], int(cell_params['hydrostatic_strain']),
-            int(cell_params['constant_volume']), float(min_height), _lib.stream()), 'snet_fire_cell_step')
+            int(cell_params['constant_volume']), float(min_height))
+    with torch.cuda.device(pos.device):
+        if hold is None:
+            _lib.check(_lib.load().snet_fire_cell_step(*args, _lib.stream()), 'snet_fire_cell_step')
+        else:
+            _lib.check(_lib.load().snet_fire_cell_step_fixed(*args, P(hold), _lib.stream()), 'snet_fire_cell_step_fixed')
 
 
 def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_below: float, params: dict, cell_params: dict,
-                   min_height: float):
+                   min_height: float, hold: Optional[np.ndarray] = None):
     """The variable-cell relaxation loop.  forces: a BatchForces, or any object with its call interface (pos, ids, cells_dev=) ->
     (graph with seg_ptr, output with `forces` fp32 [N,3] and `virial_per_system` fp64 [b,6], extra forces or None, ...), its
     counters (n_force_calls, system_steps_evaluated), `n_atoms` and `engine.dev`, and optionally `virial_extra` (fp64 [b,6] on the
     device or None: the virial that goes with the extra forces, added to the model's in the step kernel).  cells [B,3,3]: the caller's, which stay the
     reference cells.  Per step: one graph build from the device cells, one engine call, one `snet_fire_cell_step`, one readback
     (n_active).  -> (positions fp64 [N,3] and cells fp64 [B,9] on the device in the caller's order, n_steps [B], status [B] (0
-    step cap, 1 converged, 2 the kernel's guard refused the next cell), info)"""
+    step cap, 1 converged, 2 the kernel's guard refused the next cell), info).  hold (int32 [N] on the host, whole atoms:
+    `fixed.check_whole_atoms`, or None): the atoms that keep their fractional coordinates; regathered at a repack."""
     dev = forces.engine.dev
     book = RepackBook(forces.n_atoms)
     B = book.B
@@ -241,6 +262,7 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
         cell0 = torch.as_tensor(np.ascontiguousarray(np.asarray(cells, np.float64).reshape(B, 9))).to(dev)
         cell = cell0.clone()
         vel, vel_cell = torch.zeros_like(pos), torch.zeros_like(cell)
+        hold = None if hold is None else torch.as_tensor(np.ascontiguousarray(hold, np.int32)).to(dev)
         dt = torch.full((B,), float(params['dt_start']), dtype=torch.float64, device=dev)
         alpha = torch.full((B,), float(params['alpha_start']), dtype=torch.float64, device=dev)
         n_pos = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -254,7 +276,7 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
             g, out, fx = forces(pos, book.ids, cells_dev=cell)[:3]
             fire_cell_step(pos, vel, cell, vel_cell, cell0, out['forces'], out['virial_per_system'], g.seg_ptr, dt, alpha, n_pos,
                            active, n_steps, status, fmax_sys, n_active, fmax, params, cell_params, min_height, fx,
-                           getattr(forces, 'virial_extra', None))
+                           getattr(forces, 'virial_extra', None), hold)
             fire_launches += 1
             left = int(n_active.item())   # the one readback of the step
             if left == 0:
@@ -264,6 +286,7 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
                 keep, rows = book.repack(pos, act_h, st_h, cells=cell, status=status_h)
                 rows_d, keep_d = torch.as_tensor(rows).to(dev), torch.as_tensor(keep).to(dev)
                 pos, vel = pos[rows_d], vel[rows_d]   # (gathers copy: the stored slices keep the old buffers)
+                hold = None if hold is None else hold[rows_d]
                 cell, cell0, vel_cell, dt, alpha, n_pos, active, n_steps, status, fmax_sys = (
                     t[keep_d] for t in (cell, cell0, vel_cell, dt, alpha, n_pos, active, n_steps, status, fmax_sys))
         act_h, st_h, status_h = torch.stack([active, n_steps, status]).cpu().numpy()
@@ -277,7 +300,7 @@ def fire_cell_loop(forces, positions, cells, *, fmax: float, steps: int, repack_
 def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: float = 0.05, steps: int = 500,
                 repack_below: float = 0.5, extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
                 relax_cell: bool = False, scalar_pressure: float = 0.0, cell_mask=None, hydrostatic_strain: bool = False,
-                constant_volume: bool = False, **fire) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+                constant_volume: bool = False, fixed_list=None, **fire) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
     """Relax B structures with FIRE until every atom's force is below `fmax` (eV/A) or `steps` steps are done; at fixed cells,
     or with relax_cell the cells too.
 
@@ -306,7 +329,17 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
     that virial fails the step kernel's guard like any other non-finite step ('cell_failed' below).  The results gain
     `cell` [3,3] fp64 (energy, forces and stress are those at the returned positions AND cell) and `status`: 'converged',
     'steps' (the step cap) or 'cell_failed' (the step kernel refused a next cell that was not finite, inverted, or flatter than
-    cutoff / 64: the system is returned as it was before that step); `converged` is True for the first only."""
+    cutoff / 64: the system is returned as it was before that step); `converged` is True for the first only.
+
+    fixed_list: the atoms and Cartesian components that do not move (slabs, adsorbates on a frozen substrate, defects in a frozen
+    matrix, selective dynamics): per system None, a bool mask [n] or an integer index list of whole atoms, or a bool mask [n,3]
+    of components (fixed.hold_masks).  The step kernel (snet_fire_step_fixed) takes the force and the velocity of a held component
+    as 0 and never writes its position, so the returned `positions` carry the caller's bits there; `converged` then refers to the
+    free components only (a system with nothing free is converged at once, n_steps 0), while `forces` stay the model's true forces
+    at the returned positions, on held atoms too.  With relax_cell whole atoms only (a mask that holds some but not all components
+    of an atom raises ValueError): a held atom keeps its fractional coordinates and moves with the cell, as under ASE's
+    UnitCellFilter with FixAtoms.  When something is held the results gain `fixed`, a bool array [n,3]; with fixed_list None, or
+    masks that hold nothing, the call is the one without the argument: the same launches, the same dicts."""
     params = check_fire_params(fmax, steps, repack_below, fire)
     cell_params = check_cell_params(scalar_pressure, cell_mask, hydrostatic_strain, constant_volume)
     if relax_cell and extra is not None and not getattr(extra, 'provides_virial', False):
@@ -315,12 +348,15 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
                          "d3.D3DeviceTerm, SevenNetD3Calculator.relax_many(d3_term='device'))")
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
+    hold = hold_masks(fixed_list, n_at)
     if relax_cell:
+        if hold is not None:
+            check_whole_atoms(hold, n_at)
         check_cell_relax_systems(n_at, cells, pbcs, cutoff)
         forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
         final, final_cells, n_steps, status, info = fire_cell_loop(
             forces, positions, cells, fmax=fmax, steps=steps, repack_below=repack_below, params=params, cell_params=cell_params,
-            min_height=cutoff / _MAX_IMAGE_REACH)
+            min_height=cutoff / _MAX_IMAGE_REACH, hold=hold)
         g, out, _, _ = forces(final, want_atomic_virial=want_atomic_virial, with_extra=False, cells_dev=final_cells)
         info['n_force_calls'] = forces.n_force_calls
         cells_h = final_cells.cpu().numpy().reshape(-1, 3, 3)
@@ -328,13 +364,14 @@ def relax_batch(engine, types, positions, cells, pbcs, *, cutoff: float, fmax: f
         for b, res in enumerate(results):
             res['cell'] = cells_h[b].copy()
             res['status'] = STATUS_NAMES[int(status[b])]
-        return results, info
+        return (results if hold is None else attach_fixed(results, hold, g.seg_ptr_host)), info
     forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
-    final, n_steps, converged, info = fire_loop(forces, positions, fmax=fmax, steps=steps, repack_below=repack_below, params=params)
+    final, n_steps, converged, info = fire_loop(forces, positions, fmax=fmax, steps=steps, repack_below=repack_below, params=params,
+                                                hold=hold)
     g, out, _, _ = forces(final, want_atomic_virial=want_atomic_virial, with_extra=False)
     info['n_force_calls'] = forces.n_force_calls
-    results = batch_results(g, out, cells, want_atomic_virial)
-    return attach_relaxed(results, final, g.seg_ptr_host, n_steps, converged), info
+    results = attach_relaxed(batch_results(g, out, cells, want_atomic_virial), final, g.seg_ptr_host, n_steps, converged)
+    return (results if hold is None else attach_fixed(results, hold, g.seg_ptr_host)), info
 
 
 def attach_relaxed(results: List[Dict[str, Any]], final: torch.Tensor, seg_ptr_host, n_steps, converged) -> List[Dict[str, Any]]:

@@ -2,7 +2,8 @@
 """Bit identity of the batched drivers -- vibrations_many / phonons_many / elastic_many, relax_many, md_many, neb_many -- between
 two trees of this package (a refactor of their host code or of their kernels against its parent commit).
 
-    python tools/driver_identity.py TREE OUT.pkl             run the calls below with the package of TREE, pickle the results
+    python tools/driver_identity.py TREE OUT.pkl [--only relax_many,md_many]    run the calls below (or those of the named
+                                                             methods only) with the package of TREE, pickle the results
     python tools/driver_identity.py --compare A.pkl B.pkl [--report FILE]    A is the reference
 
 Each tree runs in a process of its own, on the libsnet_hip.so built in it (both may share one through SNET_HIP_LIB when no
@@ -80,7 +81,7 @@ def cases(three):
                dict(fmax=1e-4, steps=50, climb=climb), True, False)
 
 
-def run(tree, out_path):
+def run(tree, out_path, only=None):
     sys.path.insert(0, os.path.abspath(tree))
     sys.path.insert(0, os.path.join(os.path.abspath(tree), 'tests'))
     import sevennet_amd
@@ -99,7 +100,7 @@ def run(tree, out_path):
     for atomic_virial in (False, True):
         snet.compute_atomic_virial = d3.calcs[0].compute_atomic_virial = atomic_virial
         for name, method, info, args, kw, host_allowed, both_virials in cases(three):
-            if atomic_virial and not both_virials:
+            if (atomic_virial and not both_virials) or (only and method not in only):
                 continue
             for calc_name, calc, extra in (('snet', snet, {}), ('snet_d3[device]', d3, dict(d3_term='device')), ('snet_d3[host]', d3, dict(d3_term='host'))):
                 if calc is d3 and extra['d3_term'] == 'host' and not host_allowed:
@@ -162,8 +163,9 @@ def main():
     ap.add_argument('paths', nargs=2, help='TREE OUT.pkl, or with --compare: REFERENCE.pkl NEW.pkl')
     ap.add_argument('--compare', action='store_true')
     ap.add_argument('--report')
+    ap.add_argument('--only', help='comma-separated method names: run only the calls of these')
     a = ap.parse_args()
-    sys.exit(compare(a.paths[0], a.paths[1], a.report) if a.compare else run(*a.paths))
+    sys.exit(compare(a.paths[0], a.paths[1], a.report) if a.compare else run(*a.paths, only=a.only.split(',') if a.only else None))
 
 
 if __name__ == '__main__':
