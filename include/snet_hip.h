@@ -873,6 +873,49 @@ int snet_mdb_npt_step(double *pos, double *vel, double *cell, const float *force
                       double dt, double c1, double c2, uint64_t seed, int32_t phase, double max_log_volume_step, double min_height,
                       void *stream);
 
+/* ---- MD observables accumulated on the device -----------------------------------------------------
+ * What an MD driver samples while positions and velocities stay on the device (sevennet_amd.observe): pair counts of the radial
+ * distribution function, and mean-square displacement and velocity autocorrelation against a ring of origin frames.  One launch
+ * each per sample for n_sys systems; the atoms of system b are rows [seg_ptr[b], seg_ptr[b+1]) (device int32) of pos / vel (fp64
+ * [n_atoms,3]), mass (fp64 [n_atoms]) and kind (int32 [n_atoms]: the atom's kind, 0 .. kinds_b - 1, numbered within its system).
+ * All arithmetic is fp64 and no product is contracted with the sum that follows it.
+ *
+ * snet_obs_rdf adds, for every system b, to counts[off_b + (ka kinds_b + kb) bins + bin] (uint64) the number of ordered triples
+ * (i of kind ka, j of kind kb, lattice shift n) with (i != j or n != 0) whose distance falls into `bin`:
+ *   d = x_j - x_i;  f = d cell_b^-1;  f_k -= rint(f_k) on periodic axes;  d = f cell_b          (positions need not be wrapped)
+ *   for n_k in [-reach_k, reach_k] on periodic axes (0 on open ones):  r = |d + n cell_b|,  q = r / dr,  counted if q < bins in
+ *   bin (int) q,  r = sqrt((x x + y y) + z z).
+ * cell (fp64 [n_sys,9], row-major lattice vectors; rows of open axes only have to keep the cell invertible where another axis
+ * is periodic, and a cell without a periodic axis is not read).  sys_desc (int32 [n_sys,8]) = (kinds_b, off_b, pbc bits (bit k:
+ * axis k is periodic), reach_x, reach_y, reach_z, 0, 0): reach_k = floor(r_max / height_k + 0.5), r_max = bins dr, is the
+ * caller's, and with |f_k| <= 1/2 after the reduction no image within r_max lies beyond it.  tile (int32 [n_tiles,3]) = (system,
+ * first row within the system, rows): one 256-thread workgroup per tile takes the pairs (i in the tile, j in the system), counts
+ * into a uint32 histogram of kinds_b^2 bins words in LDS and adds its non-zero words to `counts` with one integer atomicAdd each
+ * -- integers only, so the result does not depend on the order of anything.  kinds_max (<= 8, kinds_max^2 bins <= 8192: the LDS
+ * histogram) and reach_max (<= 4) bound what the descriptors may say; a system or tile whose descriptor exceeds them, or points
+ * outside the system's rows or outside counts[0 .. n_counts), counts nothing.
+ *
+ * snet_obs_correlate: the ring holds `ring` = ceil(lags / origin_every) origin frames, ring_pos / ring_vel (fp64 [ring,n_atoms,3]);
+ * origin number q is sample q origin_every and sits in slot q % ring.  The CALLER stores the frame of a sample that is an origin
+ * into its slot (a device-to-device copy on the same stream) before this launch.  For sample number `sample`, grid (system, slot):
+ * the workgroup of a slot whose origin q has lag = sample - q origin_every < lags adds, for every kind of the system,
+ *   msd_sum [(kind_ptr[b] + kind) lags + lag] += sum_i |d_i|^2,            d_i = (x_i - X) - (x_i(origin) - X(origin))
+ *   vacf_sum[(kind_ptr[b] + kind) lags + lag] += sum_i (v_i - V) . (v_i(origin) - V(origin))
+ * over the system's atoms of that kind, in the fixed order of one workgroup's sum (kind_ptr int32 [n_sys+1], n_kinds rows of `lags`
+ * in msd_sum / vacf_sum, at most 8 kinds per system).  remove_com != 0: X and V are the mass-weighted centres sum m x / sum m of
+ * each frame; a system with a held component (hold, int32 [n_atoms] as for snet_mdb_step_fixed, or NULL) is anchored and not
+ * corrected, like snet_mdb_init_velocities_fixed, and a system of one free atom adds 0.  remove_com == 0: X = V = 0.  The live
+ * origins of a sample have distinct lags, so no two workgroups of a launch write one slot, and launches are ordered by the
+ * stream: a system's sums do not depend on the batch it is in.  How often lag l was added to is a matter of the schedule
+ * alone (sevennet_amd.observe.origin_counts).                                                                                  */
+int snet_obs_rdf(const double *pos, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_sys, const int32_t *kind, const double *cell,
+                 const int32_t *sys_desc, const int32_t *tile, int32_t n_tiles, double dr, int32_t bins, int32_t kinds_max,
+                 int32_t reach_max, uint64_t *counts, int64_t n_counts, void *stream);
+int snet_obs_correlate(const double *pos, const double *vel, const double *ring_pos, const double *ring_vel, const double *mass,
+                       const int32_t *hold, int64_t n_atoms, const int32_t *seg_ptr, int32_t n_sys, const int32_t *kind,
+                       const int32_t *kind_ptr, int64_t n_kinds, int32_t sample, int32_t origin_every, int32_t ring, int32_t lags,
+                       int32_t remove_com, double *msd_sum, double *vacf_sum, void *stream);
+
 /* ---- whole-model sequencer ------------------------------------------------------------------
  * replaces, for a native (C++) host, `model.forward(input_dict)` + `torch::autograd::grad(...)` of
  * the LAMMPS pair styles (sevenn/pair_e3gnn/pair_e3gnn.cpp:200-207, pair_e3gnn_parallel.cpp:424-503)

@@ -201,6 +201,10 @@ SIGNATURES = {
     'snet_mdb_npt_step': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, c_i32p, C.c_int32,
                                     c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p, C.c_double, C.c_double,
                                     C.c_double, C.c_uint64, C.c_int32, C.c_double, C.c_double, c_stream]),
+    'snet_obs_rdf': (C.c_int, [c_f64p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, C.c_int32, C.c_double, C.c_int32,
+                               C.c_int32, C.c_int32, C.c_void_p, C.c_int64, c_stream]),
+    'snet_obs_correlate': (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i32p,
+                                     C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f64p, c_stream]),
     'snet_nl_grid': (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     'snet_nl_bin': (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p, C.c_int64,
                               C.c_void_p, c_i32p, c_i32p, c_stream]),

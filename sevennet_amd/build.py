@@ -30,7 +30,7 @@ _sfx = ('_' + os.path.basename(LIB).replace('.so', '')) if os.environ.get('SNET_
 GEN = os.path.join(CSRC, 'generated' + _sfx)
 OBJ = os.path.join(CSRC, 'build' + _sfx)
 ARCH = 'gfx950'
-STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_lastlayer.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_vib.hip', 'snet_phonon.hip', 'snet_elastic.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_md.hip', 'snet_d3.hip', 'snet_d3_ref.cpp']
+STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_lastlayer.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_vib.hip', 'snet_phonon.hip', 'snet_elastic.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_observe.hip', 'snet_md.hip', 'snet_d3.hip', 'snet_d3_ref.cpp']
 
 
 def _rocm_root() -> str:

@@ -421,7 +421,10 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         `status`: 'ok' or 'cell_failed' (md_batch).
         fixed_list: per system None, a bool mask [n] or an index list of atoms, or a bool mask [n,3] of Cartesian components that
         do not move: no kick, no drift, no noise, velocity 0 (held components of `velocities` are set to 0), `temperature`
-        over the remaining degrees of freedom; the dicts gain `fixed` [n,3].  Not together with pressure= (md_batch)."""
+        over the remaining degrees of freedom; the dicts gain `fixed` [n,3].  Not together with pressure= (md_batch).
+        observe: an observe.Observe -- RDF pair counts, mean-square displacement and velocity autocorrelation accumulated on the
+        GPU every `every` steps, nothing read back before the end; the dicts gain `observables` (observe.attach_observables), its
+        `kinds` as atomic numbers.  Not together with pressure= (md_batch)."""
         from .md import md_batch
         if not len(numbers_list) == len(positions_list) == len(masses_list):
             raise ValueError(f'{len(numbers_list)} atomic-number arrays, {len(positions_list)} position arrays and '
@@ -429,6 +432,12 @@ class SevenNetCalculator(ManyAtomsMixin, Calculator):
         results, self.md_info = md_batch(self.model, self._types_list(numbers_list), list(positions_list), list(masses_list), cells,
                                          pbcs, cutoff=self.cutoff, dt=dt, steps=steps,
                                          want_atomic_virial=self.compute_atomic_virial, **kw)
+        if kw.get('observe') is not None:   # kinds: the model's species indices -> atomic numbers
+            z_of = {t: z for z, t in self.type_map.items()}
+            for r in results:
+                kinds = r['observables']['kinds']
+                if kinds is not None:
+                    r['observables']['kinds'] = np.array([z_of[int(t)] for t in kinds], np.int64)
         return results
 
     def calculate(self, atoms=None, properties=None, system_changes=all_changes):

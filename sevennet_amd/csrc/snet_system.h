@@ -1,6 +1,9 @@
 // Device helpers of the fp64 driver kernels that give one 256-thread workgroup to a system (or a copy, a row, an image):
 // snet_relax.hip, snet_relax_cell.hip, snet_mdstep.hip, snet_mdnpt.hip, snet_neb.hip, snet_vib.hip, snet_phonon.hip and
-// snet_elastic.hip.  One definition each of what those kernels share.
+// snet_elastic.hip.  One definition each of what those kernels share.  snet_observe.hip (the MD observables) stands on them too:
+// `segment`, `block_sum`, `held_bits` and the 3x3 helpers.  Its own sums are written under contract(off); the products inside
+// det3 / inv3 / row_mul contract as they do everywhere, which its integer pair counts do not see (a pair is never that close to a
+// bin edge where the counts are compared) and its correlation sums do not go through.
 //
 // Contraction is part of the arithmetic.  vib, phonon and elastic equal their numpy restatements bit for bit because no product
 // of theirs is contracted with the sum that follows it; relax, relax_cell, mdstep, mdnpt and neb compute under the HIP default.

@@ -539,7 +539,7 @@ class SevenNetD3Calculator(ManyAtomsMixin, _SumBase):
         virial then enters the barostat's pressure, and the D3 share of the results is evaluated at the returned cells.  With
         'host' it raises ValueError.
         fixed_list (SevenNetCalculator.md_many) goes through with either d3_term: held components feel neither the model's nor the
-        D3 forces."""
+        D3 forces.  observe (SevenNetCalculator.md_many) goes through with either d3_term too: the dicts gain `observables`."""
         self._check_d3_term(d3_term)
         npt = kw.get('pressure') is not None
         if npt and d3_term == 'host':

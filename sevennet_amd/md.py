@@ -17,7 +17,11 @@ tests/md_ref.py.  Units: eV, A, fs, amu, K.
 With a `pressure`, `md_batch` runs isotropic NPT (`md_npt_loop`): one `snet_mdb_npt_step` launch (csrc/snet_mdnpt.hip) per step
 adds the stochastic cell rescaling of Bernetti and Bussi (J. Chem. Phys. 153, 114107 (2020)) between the kicks and the drift, on
 the engine's per-system virial; the cells stay on the device, where the batched neighbor kernels read them.  That rule is
-written out in include/snet_hip.h (snet_mdb_npt_step) and restated in tests/md_npt_ref.py."""
+written out in include/snet_hip.h (snet_mdb_npt_step) and restated in tests/md_npt_ref.py.
+
+With an `observe` (sevennet_amd.observe.Observe), the fixed-cell loop samples (x_k, v_k) every few steps into accumulators of the
+radial distribution function, the mean-square displacement and the velocity autocorrelation on the device (snet_obs_rdf,
+snet_obs_correlate), and the results gain `observables`."""
 from __future__ import annotations
 
 import math
@@ -29,6 +33,7 @@ import torch
 from . import _lib
 from .batch import _MAX_IMAGE_REACH, BatchForces, _as_host, batch_results, system_of, validate_batch_inputs
 from .fixed import attach_fixed, held_components, hold_masks
+from .observe import Accumulator, Observe, attach_observables, observe_plan as make_observe_plan
 from .relax import check_cell_relax_systems
 
 ACC = 9.648533212e-3    # eV / (A amu) in A / fs^2
@@ -242,11 +247,13 @@ def md_npt_step(pos: torch.Tensor, vel: torch.Tensor, cell: torch.Tensor, forces
 
 def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray, *,
             dt: float, steps: int, friction: float, seed: int, log_every: int, traj_every: int, remove_com: bool,
-            want_atomic_virial: bool, hold: Optional[np.ndarray] = None):
+            want_atomic_virial: bool, hold: Optional[np.ndarray] = None, observe_plan: Optional[dict] = None):
     """The MD loop over the force call `forces` (a BatchForces on validated inputs; `validate_md_inputs`) -> (graph and engine
     output of the last force call, dict of device tensors: pos, vel [N,3], e_pot, e_kin [samples,B], traj [frames,N,3] or None,
     step_index [B]; info).  hold (int32 [N] on the host, fixed.hold_masks, or None): the components held fixed; the held
-    components of vel0 are taken as 0."""
+    components of vel0 are taken as 0.  observe_plan (observe.observe_plan, or None): (x_k, v_k) is sampled at every step k that is a
+    multiple of its `every` -- that step's launch is split into its FINISH half, the observe launches and its START half, which is
+    the same arithmetic because the kernel stores exact fp64 in between -- and the state gains `observe`, the Accumulator."""
     dev = forces.engine.dev
     n_atoms = forces.n_atoms
     B, steps, log_every, traj_every = len(n_atoms), int(steps), int(log_every), int(traj_every)
@@ -268,20 +275,34 @@ def md_loop(forces: BatchForces, positions, mass: np.ndarray, vel0: Optional[np.
         e_pot_log = torch.zeros(steps // log_every + 1, B, dtype=torch.float64, device=dev)
         e_kin_log = torch.zeros_like(e_pot_log)
         traj = torch.zeros(steps // traj_every + 1, N, 3, dtype=torch.float64, device=dev) if traj_every > 0 else None
+        observer = None if observe_plan is None else Accumulator(observe_plan, m_d, seg, hold_d, dev)
+        n_launches = 0
         g = out = None
         for k in range(steps + 1):
             last = k == steps
             g, out, fx, ex = forces(pos, want_atomic_virial=want_atomic_virial and last)
             if traj is not None and k % traj_every == 0:
                 traj[k // traj_every].copy_(pos)   # x_k: the launch below moves on to x_{k+1}
-            md_step(pos, vel, out['forces'], m_d, seg, id_d, kT_d, step_index, e_kin, dt, c1, c2, seed,
-                    (FINISH if k > 0 else 0) | (0 if last else START), fx, hold_d)
+            phase = (FINISH if k > 0 else 0) | (0 if last else START)
+            # a sampled step: (x_k, v_k) stands between the finishing kick and the drift -- `vel` holds v_k after a FINISH launch
+            # (step 0: as it is), `pos` holds x_k until a START launch
+            sampled = observer is not None and k % observer.obs.every == 0
+            halves = ([p for p in (FINISH, START) if phase & p] or [0]) if sampled else [phase]
+            if sampled and not phase & FINISH:
+                observer.sample(pos, vel)
+            for half in halves:
+                md_step(pos, vel, out['forces'], m_d, seg, id_d, kT_d, step_index, e_kin, dt, c1, c2, seed, half, fx, hold_d)
+                n_launches += 1
+                if sampled and half == FINISH:
+                    observer.sample(pos, vel)
             if k % log_every == 0:   # e_kin is the kinetic energy of v_k, the potential energy that of x_k
                 j = k // log_every
                 e_pot_log[j].copy_(out['energy_per_system'] if ex is None else out['energy_per_system'] + ex)
                 e_kin_log[j].copy_(e_kin)
-    info = dict(n_force_calls=forces.n_force_calls, md_launches=steps + 1, system_steps_evaluated=forces.system_steps_evaluated)
-    return g, out, dict(pos=pos, vel=vel, e_pot=e_pot_log, e_kin=e_kin_log, traj=traj, step_index=step_index), info
+    info = dict(n_force_calls=forces.n_force_calls, md_launches=n_launches, system_steps_evaluated=forces.system_steps_evaluated)
+    if observer is not None:
+        info['observe_samples'] = observer.n_samples
+    return g, out, dict(pos=pos, vel=vel, e_pot=e_pot_log, e_kin=e_kin_log, traj=traj, step_index=step_index, observe=observer), info
 
 
 def md_npt_loop(forces: BatchForces, positions, cells, mass: np.ndarray, vel0: Optional[np.ndarray], kT: np.ndarray, ids: np.ndarray,
@@ -373,7 +394,8 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
              friction: float = 0.0, velocities=None, seed: int = 0, log_every: int = 1, traj_every: int = 0, remove_com: bool = True,
              extra: Optional[Callable] = None, n_atoms=None, want_atomic_virial: bool = False,
              system_ids=None, pressure=None, compressibility=None, barostat_time: float = 1000.0,
-             max_log_volume_step: float = 0.1, fixed_list=None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
+             max_log_volume_step: float = 0.1, fixed_list=None,
+             observe: Optional[Observe] = None) -> Tuple[List[Dict[str, Any]], Dict[str, int]]:
     """`steps` MD steps of `dt` fs for B structures: NVE (friction 0) or Langevin at `temperature` at fixed cells, or with
     `pressure` isotropic NPT, the cells moving on the device.
 
@@ -421,12 +443,25 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     a system with nothing held keeps 3 n.  `forces` stay the model's true forces, on held atoms too.  Together with `pressure`
     fixed_list raises ValueError: constant-pressure MD with frozen atoms is not a defined ensemble here.  When something is held
     the results gain `fixed`, a bool array [n,3]; with fixed_list None, or masks that hold nothing, the call is the one without
-    the argument: the same launches, the same dicts."""
+    the argument: the same launches, the same dicts.
+
+    observe (observe.Observe; None: nothing is sampled, the launches and dicts above): the radial distribution function, the
+    mean-square displacement and the velocity autocorrelation function accumulated on the device (sevennet_amd.observe;
+    snet_obs_rdf, snet_obs_correlate).  (x_k, v_k) is sampled at every step k that is a multiple of observe.every, v_k after the
+    finishing half kick: steps // every + 1 samples.  The launch of a sampled step is issued in its two halves around the
+    observe launches (`info['md_launches']` counts them, `info['observe_samples']` the samples); positions, velocities, `e_pot`,
+    `e_kin` and `trajectory` keep the bits of the run without `observe`.  Each dict gains `observables`
+    (observe.attach_observables).  Together with `pressure` it raises ValueError: displacements under a rescaled cell are not
+    defined here, and the constant-pressure RDF is not provided."""
     types, positions, n_at, cells, pbcs = validate_batch_inputs(types, positions, cells, pbcs, cutoff, engine.spec.num_species,
                                                                 n_atoms=n_atoms)
     mass, vel0, kT, ids = validate_md_inputs(masses, n_at, dt, steps, temperature, friction, velocities, seed, log_every, traj_every,
                                              system_ids)
     hold = hold_masks(fixed_list, n_at)
+    if observe is not None and pressure is not None:
+        raise ValueError('observe with pressure: the mean-square displacement under a rescaled cell is not defined here, and the '
+                         'constant-pressure RDF is not provided; run at fixed cells, or without observe')
+    plan = None if observe is None else make_observe_plan(observe, types, n_at, cells, pbcs)
     if pressure is not None:
         if fixed_list is not None:
             raise ValueError('fixed_list with pressure: constant-pressure MD with atoms held fixed is not a defined ensemble here '
@@ -444,6 +479,8 @@ def md_batch(engine, types, positions, masses, cells, pbcs, *, cutoff: float, dt
     forces = BatchForces(engine, types, n_at, cells, pbcs, cutoff, extra)
     g, out, state, info = md_loop(forces, positions, mass, vel0, kT, ids, dt=dt, steps=steps, friction=friction, seed=seed,
                                   log_every=log_every, traj_every=traj_every, remove_com=remove_com,
-                                  want_atomic_virial=want_atomic_virial, hold=hold)
+                                  want_atomic_virial=want_atomic_virial, hold=hold, observe_plan=plan)
     results = attach_md(batch_results(g, out, cells, want_atomic_virial), state, g.seg_ptr_host, n_at, hold)
+    if plan is not None:
+        attach_observables(results, plan, state['observe'].to_host(), dt)
     return (results if hold is None else attach_fixed(results, hold, g.seg_ptr_host)), info
