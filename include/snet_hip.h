@@ -232,6 +232,40 @@ int snet_edge_tiles(const int32_t *row_ptr, int64_t n_dst, int32_t *tile_ptr, in
 int snet_edge_tiles_packed(const int32_t *row_ptr, int64_t node_begin, int64_t node_end, int32_t *tile_e0,
                            int32_t *tile_nodes, int64_t tile_capacity, int64_t *n_tiles, void *stream);
 int snet_fused_plan_tile_mode(const snet_fused_plan *plan);
+/* ---- merged g_xe stores -------------------------------------------------------------------------------------------------
+ * A workgroup of the tangent-mode reverse kernel takes `window` consecutive tiles of its launch's list (a WINDOW, counted from the
+ * start of the list), and neighbouring destination rows share sources: the g_xe rows of a window that have the same source are added
+ * in LDS and written ONCE, into a compact buffer g_xe[n_rows, dx], which the segment sum then reads instead of one row per edge.
+ *   snet_fused_plan_merge_window   tiles per window of this plan's merged-store kernel; 0: the shape has none (only the packed-tile
+ *                                  class in tangent mode does) and the host keeps snet_conv_bwd_fused_tangent
+ *   snet_gxe_merge_map             per graph, beside the tile list.  The list is tile_ptr / tile_node / n_tiles in the plan's tile
+ *                                  mode (0: snet_edge_tiles, 1: snet_edge_tiles_packed), launched as the sub-lists [0, tile_cut) and
+ *                                  [tile_cut, n_tiles) (tile_cut = 0: one launch): no window straddles the cut.  n_dst rows of row_ptr,
+ *                                  sources in [0, n_src).  Outputs (device):
+ *                                    merge_row[E]   row of the compact buffer the edge OWNS -- the first edge of its window, in edge
+ *                                                   order, with its source -- or -1
+ *                                    merge_next[E]  slot (16 x tile of the window + place in the tile) of the next edge of the window
+ *                                                   with the same source, -1: none.  An owner's chain is summed in slot order, whatever
+ *                                                   the multiplicity (several periodic images of one source in one row included)
+ *                                    seg_ptr[n_src + 1], perm[n_rows <= E]  the merged rows of every source, as
+ *                                                   snet_segment_sum_rows_chunked takes col_ptr / eperm
+ *                                    *n_rows        merged rows in all
+ *                                  It reads the index arrays back and synchronises the stream (topology only, once per graph).
+ *   snet_gxe_merge_map_host        the same on host arrays, no device involved
+ *   snet_conv_bwd_fused_tangent_merged  snet_conv_bwd_fused_tangent with g_xe[n_rows, dx] compact (required); g_vec bit for bit the
+ *                                  same.  Rows keep the kernel's chunk order (snet_fused_plan_gxe_chunks). */
+int snet_fused_plan_merge_window(const snet_fused_plan *plan);
+int snet_gxe_merge_map(const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles,
+                       int64_t tile_cut, int32_t tile_mode, int32_t window, int64_t n_dst, int64_t n_src, int64_t n_edges,
+                       int32_t *merge_row, int32_t *merge_next, int32_t *seg_ptr, int32_t *perm, int64_t *n_rows, void *stream);
+int snet_gxe_merge_map_host(const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node,
+                            int64_t n_tiles, int64_t tile_cut, int32_t tile_mode, int32_t window, int64_t n_src, int64_t n_edges,
+                            int32_t *merge_row, int32_t *merge_next, int32_t *seg_ptr, int32_t *perm, int64_t *n_rows);
+int snet_conv_bwd_fused_tangent_merged(const snet_fused_plan *plan, const float *x, const float *sh, const float *dsh, const float *h2,
+                                       const float *h2d, const int32_t *w_row, const int32_t *row_ptr, const int32_t *src,
+                                       const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles, float scale,
+                                       const float *g_out, float *g_xe, const int32_t *merge_row, const int32_t *merge_next,
+                                       const float *edge_vec, float *g_vec, const float *x_rowmax, const float *g_rowmax, void *stream);
 /* Scalar-output shapes (every path (l, l -> 0): the last interaction layer): the source-row gradient
  *   g_x[j] = sum over the edges e that have j as their source of  w_e * T * Y(e) * g_out[center(e)]
  * is itself a uvu convolution -- shape `tag` (x = the g_out row, out = g_x), radial weights W2 with column c scaled by
@@ -969,6 +1003,11 @@ int snet_model_set_layer0_moments(snet_model *model, int32_t enable);
  * its file carries the metadata key last_layer_merged=1 and the shape passes snet_lastlayer_plan_create.  Applies to the following
  * evaluations.  For A/B runs and tests. */
 int snet_model_set_last_layer_merged(snet_model *model, int32_t enable);
+/* the middle layers' g_xe rows merged inside the reverse kernel (snet_conv_bwd_fused_tangent_merged over snet_gxe_merge_map;
+ * enable != 0, the default unless SNET_GXE_MERGE=0 is in the environment at load time) or one row per edge (0).  Taken where the
+ * topology cache is on (the map is kept with the tile list), the layer's shape has the kernel and the graph's merged rows are at most
+ * 0.8 of its edges (an atom order without locality merges nothing).  Applies to the following evaluations.  For A/B runs and tests. */
+int snet_model_set_gxe_merge(snet_model *model, int32_t enable);
 int snet_model_topology_changed(snet_model *model);
 int64_t snet_model_eval_syncs(const snet_model *model);
 int snet_model_set_halo(snet_model *model, snet_halo_fn forward, snet_halo_fn reverse, void *user,

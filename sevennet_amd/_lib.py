@@ -105,6 +105,14 @@ SIGNATURES = {
     'snet_conv_bwd_fused_tangent': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p,
                                               c_i32p, C.c_int64, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                               c_stream]),
+    'snet_fused_plan_merge_window': (C.c_int, [C.c_void_p]),
+    'snet_gxe_merge_map': (C.c_int, [c_i32p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                     C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64), c_stream]),
+    'snet_gxe_merge_map_host': (C.c_int, [c_i32p, c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, C.POINTER(C.c_int64)]),
+    'snet_conv_bwd_fused_tangent_merged': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                                     c_i32p, C.c_int64, C.c_float, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
+                                                     c_f32p, c_stream]),
     'snet_model_set_layer0_moments': (C.c_int, [C.c_void_p, C.c_int32]),
     'snet_layer0_plan_create': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
     'snet_layer0_fold': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
@@ -113,6 +121,7 @@ SIGNATURES = {
     'snet_layer0_conv_bwd': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p,
                                        C.c_int64, c_f32p, c_f32p, c_stream]),
     'snet_model_set_last_layer_merged': (C.c_int, [C.c_void_p, C.c_int32]),
+    'snet_model_set_gxe_merge': (C.c_int, [C.c_void_p, C.c_int32]),
     'snet_lastlayer_plan_create': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     'snet_lastlayer_plan_destroy': (None, [C.c_void_p]),
     'snet_lastlayer_conv_bwd': (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_i32p,

@@ -19,7 +19,7 @@ import sys
 from typing import List
 
 from . import codegen, codegen_fused
-from .shapes import aot_conv_specs, lastlayer_test_configs
+from .shapes import aot_conv_specs, lastlayer_test_configs, merged_store_test_tags
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
@@ -30,7 +30,7 @@ _sfx = ('_' + os.path.basename(LIB).replace('.so', '')) if os.environ.get('SNET_
 GEN = os.path.join(CSRC, 'generated' + _sfx)
 OBJ = os.path.join(CSRC, 'build' + _sfx)
 ARCH = 'gfx950'
-STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_lastlayer.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_vib.hip', 'snet_phonon.hip', 'snet_elastic.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_observe.hip', 'snet_md.hip', 'snet_d3.hip', 'snet_d3_ref.cpp']
+STATIC_SOURCES = ['snet_api.cpp', 'snet_model.cpp', 'snet_halo.cpp', 'snet_gemm.hip', 'snet_mlp.hip', 'snet_layer0.hip', 'snet_lastlayer.hip', 'snet_edge.hip', 'snet_node.hip', 'snet_force.hip', 'snet_neighbor.hip', 'snet_batch.hip', 'snet_relax.hip', 'snet_relax_cell.hip', 'snet_neb.hip', 'snet_vib.hip', 'snet_phonon.hip', 'snet_elastic.hip', 'snet_mdstep.hip', 'snet_mdnpt.hip', 'snet_observe.hip', 'snet_md.hip', 'snet_gxemerge.cpp', 'snet_d3.hip', 'snet_d3_ref.cpp']
 
 
 def _rocm_root() -> str:
@@ -152,6 +152,7 @@ def build(jobs: int = 0, force: bool = False, extra_configs=(), verbose: bool = 
     specs = aot_conv_specs(list(extra_configs) + list(lastlayer_test_configs().values()))   # (+ the test-only shapes)
     sources = [os.path.join(CSRC, s) for s in STATIC_SOURCES]
     keep = set()
+    merged_tests = set(merged_store_test_tags())
     for tag, spec in specs.items():
         path = os.path.join(GEN, f'conv_{tag}.hip')
         codegen.write_if_changed(path, codegen.gen_conv(spec))
@@ -166,8 +167,13 @@ def build(jobs: int = 0, force: bool = False, extra_configs=(), verbose: bool = 
             codegen.write_if_changed(tpath, codegen_fused.gen_conv_fused_tangent(spec))
             sources.append(tpath)
             keep.add(os.path.basename(tpath))
+            if codegen_fused.merged_store_class(spec) or tag in merged_tests:   # ... and its merged-store instantiation: a third
+                mpath = os.path.join(GEN, f'convftm_{tag}.hip')
+                codegen.write_if_changed(mpath, codegen_fused.gen_conv_fused_tangent_merged(spec))
+                sources.append(mpath)
+                keep.add(os.path.basename(mpath))
     for f in os.listdir(GEN):  # drop stale generated shapes
-        if (f.startswith('conv_') or f.startswith('convf_') or f.startswith('convft_') or f.startswith('_conv')) and f not in keep:
+        if (f.startswith('conv_') or f.startswith('convf_') or f.startswith('convft_') or f.startswith('convftm_') or f.startswith('_conv')) and f not in keep:
             os.remove(os.path.join(GEN, f))
     jobs = jobs or min(16, os.cpu_count() or 4)
     if verbose:

@@ -244,8 +244,13 @@ class _Gen:
     (prologue / block top / sub-step / block end / hidden-layer tail / epilogue), forward kernel (prologue / pass top / block),
     launchers."""
 
-    def __init__(self, spec: ConvSpec, tangent: bool = False):
+    def __init__(self, spec: ConvSpec, tangent: bool = False, merged: bool = False):
         self.spec = spec
+        # merged: the MERGED-STORE instantiation of the tangent-mode kernel (`gen_conv_fused_tangent_merged`, translation unit
+        # convftm_<tag>.hip): rows of g_xe that share their source inside the workgroup's window of tiles are added in LDS and leave
+        # the chip once.  Nothing the two other generators emit reads this flag.
+        assert tangent or not merged
+        self.MG = bool(merged)
         # tangent: generate the TANGENT-MODE reverse kernel (`gen_conv_fused_tangent`, its own translation unit convft_<tag>.hip) instead
         # of the kernels of `gen_conv_fused`, whose text does not depend on anything below that reads this flag
         self.TG = bool(tangent)
@@ -337,7 +342,10 @@ class _Gen:
         # occupancy this shape runs at (the lmax-3 shapes sit at 256 already and spilled 200+ registers with it)
         budget = (168 if self.three_waves else 256) - 24   # margin: the estimate is a lower bound of what hipcc's allocator ends up with
         xp_regs = max([4 * b_['U'] * (2 * b_['cat'].l1 + 1) for b_ in bsched[1:]] or [0])
-        self.XPF = VMORD and len(bsched) > 1 and live + xp_regs + 8 <= budget and not OPTS.get('noxpf')
+        # (merged stores: the owners' chain reads at a block end are another U d1 vector registers in flight there -- with both, the
+        # SevenNet-0 middle layer spilled 12 registers; without this prefetch it needs 250 and spills none)
+        mg_regs = max(4 * b_['U'] * (2 * b_['cat'].l1 + 1) for b_ in bsched) if self.MG else 0
+        self.XPF = VMORD and len(bsched) > 1 and live + mg_regs + xp_regs + 8 <= budget and not OPTS.get('noxpf')
         # the hoisted slab request keeps the staging registers live across the block boundary: same budget rule
         self.HOIST = VMORD and live + 16 + 8 <= budget and not OPTS.get('nohoist')
         # x blocks with 2 l + 1 >= noxn get no register prefetch of the next block's source rows.  Default: the l = 3 blocks of the
@@ -626,12 +634,12 @@ def _rev_prologue(cx: _Gen):
         A('// multiply-add per register.  No operand split of g_w, no g_h2 products, no second W2 image in the slab, no hidden-layer tail, no')
         A('// g_emb: the sum goes, along r_e / |r_e|, straight into the g_vec row the kernel writes anyway.')
     A('template <int NT, bool F16, int NWV, bool GLDS, int OCC, bool GX>')
-    A(f'__global__ __launch_bounds__(64 * NWV, OCC) void conv_bwdf{"t" if TG else ""}_{tag}(const float *__restrict__ x, const float *__restrict__ sh,')
+    A(f'__global__ __launch_bounds__(64 * NWV, OCC) void conv_bwdf{("tm" if cx.MG else "t") if TG else ""}_{tag}(const float *__restrict__ x, const float *__restrict__ sh,')
     A('    const float *__restrict__ dsh, const float *__restrict__ h2, const int32_t *__restrict__ w_row,')
     A('    const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ src, const int32_t *__restrict__ tile_ptr,')
     A('    const int32_t *__restrict__ tile_node, int n_tiles, const u32x4 *__restrict__ slabs, float scale,')
     A('    const float *__restrict__ g_out, float *__restrict__ g_xe, float *__restrict__ g_h2, float *__restrict__ g_vec,')
-    A('    const snet::FusedTail tail, int diag) {')
+    A('    const snet::FusedTail tail, int diag' + (', const int32_t *__restrict__ merge_row, const int32_t *__restrict__ merge_next' if cx.MG else '') + ') {')
     A('  // diag: always 0 in production (bit 0 also serves as the opaque branch condition around the tensor-product bodies);')
     A('  // kernel-tuning builds: 1 skip the tensor product, 2 skip the g_h2 products, 4 skip the w products, 8 skip the')
     A('  // g_out loads, 16 skip the g_xe stores -- timing decomposition, results are then garbage')
@@ -708,6 +716,8 @@ def _rev_prologue(cx: _Gen):
         A('  const int in_b = e >= e_b ? 1 : 0;')
     A('  const int s_src = src[e];')
     A('  const int wr = w_row ? w_row[e] : e;')
+    if cx.MG:
+        _rev_merge_prologue(cx)
     A('  float x_bound = 0.f;')
     A('  if constexpr (F16) x_bound = tail.x_max[s_src] * tail.g_max[' + ('in_b ? node_b : node' if XT else 'node') + '];')
     _c0, _U0 = cats[0], bsched[0]['U']
@@ -815,6 +825,85 @@ def _rev_prologue(cx: _Gen):
     S(0, '  ')
 
 
+MERGE_DEPTH = 2   # contributors of a merged row that the owner adds in straight-line code; a longer chain takes the loop behind it
+
+
+def _rev_merge_prologue(cx: _Gen):
+    """merged stores: the edge's entry of the merge map (snet_gxe_merge_map) and the workgroup's LDS buffer of parked g_x values"""
+    A = cx.A
+    MXC = 16 * max(bs['U'] * (2 * bs['cat'].l1 + 1) for bs in cx.bsched)   # columns of the widest block
+    A('  // MERGED STORES.  The workgroup\'s NWV tiles are one window of the merge map: slot = 16 wave + j.  Edges of the window that share')
+    A('  // their source share ONE row of the compact g_xe buffer, owned by the first of them in slot order (merge_row[e] >= 0; -1 for the')
+    A('  // others); merge_next[e] is the slot of the next edge of the window with the same source (-1: none).  At the end of a block the')
+    A('  // non-owners park their g_x values here, the block\'s last barrier passes, and every owner adds its chain in slot order -- a fixed')
+    A('  // order, so two launches give the same bits -- before its 16-byte stores.  "None" is the slot M_NONE, a row of zeros that points')
+    A('  // to itself: the first links of every chain are then added without a branch.')
+    A('  const int m_row = valid ? merge_row[e] : -1;')
+    A(f'  constexpr int MXC = {MXC}, M_NONE = 16 * NWV;')
+    A('  __shared__ int s_mnext[M_NONE + 1];')
+    A('  __shared__ __attribute__((aligned(16))) float s_mx[M_NONE + 1][MXC];')
+    A('  {')
+    A('    const int nx_ = valid ? merge_next[e] : -1;')
+    A('    if (g == 0) s_mnext[16 * wave + j] = nx_ < 0 ? M_NONE : nx_;   // (visible behind the prologue\'s barrier, like the row of zeros)')
+    A('    if (tid == 0) s_mnext[M_NONE] = M_NONE;')
+    A('    if (tid < MXC / 4) *reinterpret_cast<f32x4 *>(&s_mx[M_NONE][4 * tid]) = f32x4{0.f, 0.f, 0.f, 0.f};')
+    A('  }')
+
+
+def _rev_merge_park(cx: _Gen, ci: int):
+    """merged stores, in front of the last barrier of block ci: g_x back to scale, the non-owners' values into the window's buffer"""
+    A = cx.A
+    cat, U, ncb, d1, _ = cx.block_info(ci)
+    if len(cx.bsched[ci]['steps']) == 1:
+        # (a one-sub-step block has no barrier between the previous block's chain reads and this park: it gets one)
+        A('      __syncthreads();')
+    A('      if constexpr (F16) {   // the bodies ran on raw matrix accumulators and scaled g_out entries: back to g_x itself')
+    A('#pragma unroll')
+    A(f'        for (int u = 0; u < {U}; ++u)')
+    A('#pragma unroll')
+    A(f'          for (int m = 0; m < {d1}; ++m) gx[u][m] *= gx_fix;')
+    A('      }')
+    A('      if (valid && m_row < 0) {')
+    A('        float *mp_ = &s_mx[16 * wave + j][4 * g];')
+    for u in range(U):
+        for m in range(d1):
+            A(f'        *reinterpret_cast<f32x4 *>(mp_ + {16 * (u * d1 + m)}) = gx[{u}][{m}];')
+    A('      }')
+
+
+def _rev_merge_stores(cx: _Gen, ci: int):
+    """merged stores of block ci: every owner adds the parked values of its chain, then writes its row of the compact buffer"""
+    A = cx.A
+    cat, U, ncb, d1, _ = cx.block_info(ci)
+    # The first MERGE_DEPTH links are straight-line code for every lane (a chain that has ended reads the row of zeros, a non-owner's
+    # sums are dropped); only a longer chain -- more than MERGE_DEPTH + 1 edges of one source in a window: small periodic cells --
+    # enters a loop, one stored value at a time.  (A loop over the whole chain at every block end cost 12 spilled registers in the
+    # SevenNet-0 middle layer, whichever way it was arranged; this form has none.)
+    A('    {')
+    A('      const int nx1 = s_mnext[16 * wave + j];')
+    for d in range(2, MERGE_DEPTH + 2):
+        A(f'      const int nx{d} = s_mnext[nx{d - 1}];')
+    for d in range(1, MERGE_DEPTH + 1):
+        A(f'      const float *mp{d} = &s_mx[nx{d}][4 * g];')
+    A(f'      float *o = g_xe + (size_t)max(m_row, 0) * DX + {cat.x_off} + {16 * d1 * U} * cb + 4 * g;   // chunk order [tile][component]: GXE_CHUNK')
+    for u in range(U):
+        for m in range(d1):
+            k = u * d1 + m
+            for d in range(1, MERGE_DEPTH + 1):   # slot order
+                A(f'      gx[{u}][{m}] += *reinterpret_cast<const f32x4 *>(mp{d} + {16 * k});')
+    A(f'      if (__builtin_expect(m_row >= 0 && nx{MERGE_DEPTH + 1} != M_NONE, 0)) {{')
+    for u in range(U):
+        for m in range(d1):
+            A(f'        for (int nx = nx{MERGE_DEPTH + 1}; nx != M_NONE; nx = s_mnext[nx]) gx[{u}][{m}] += *reinterpret_cast<const f32x4 *>(&s_mx[nx][{16 * (u * d1 + m)} + 4 * g]);')
+    A('      }')
+    A('      if (m_row >= 0) {')
+    for u in range(U):
+        for m in range(d1):
+            A(f'        __builtin_nontemporal_store(gx[{u}][{m}], reinterpret_cast<f32x4 *>(o + {16 * (u * d1 + m)}));')
+    A('      }')
+    A('    }')
+
+
 def _rev_block_top(cx: _Gen, ci: int):
     """x block ci: its first rows, then -- per block of U channel tiles -- the requests of the NEXT block's rows and g_out entries"""
     A, exp, XT, XPF, bsched = cx.A, cx.exp, cx.XT, cx.XPF, cx.bsched
@@ -870,7 +959,7 @@ def _rev_block_top(cx: _Gen, ci: int):
     S(1, '    ')
 
 
-def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
+def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb, last: bool = False):
     """one sub-step = two 16-column tiles of W2: per tile  w = W2^T h2^T (matrix cores) -> reverse tensor-product body; then the
     operand split of the two g_w tiles and  g_h2^T += W2 g_w^T;  the next sub-step's slab is parked, one workgroup barrier"""
     A, spec, exp, ST, STL, HOIST = cx.A, cx.spec, cx.exp, cx.ST, cx.STL, cx.HOIST
@@ -942,6 +1031,8 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
     if ST and not STL:
         A('      asm volatile("" :: "v"(ga[0][0]), "v"(ga[1][0]), "v"(ga[2][0]), "v"(ga[3][0]));')
     S(7)
+    if cx.MG and last:   # merged stores: the block's g_x values are complete -- parked in front of the sub-step's own barrier
+        _rev_merge_park(cx, ci)
     A('      if (sidx + 1 < NSUB' + (' && !(diag & 32)' if exp else '') + ') stage_store((buf ^ 1));')
     S(8)
     A(('      if (!(diag & 128)) ' if exp else '      ') + '__syncthreads();')
@@ -951,16 +1042,10 @@ def _rev_substep(cx: _Gen, ci: int, si_: int, ta, tb):
     A('    }')
 
 
-def _rev_block_end(cx: _Gen, ci: int):
-    """g_xe stores of the block (behind the hoisted slab request), the next block's g_out entries parked, rows rotated"""
-    A, exp, STL, HOIST, bsched, gxe_std = cx.A, cx.exp, cx.STL, cx.HOIST, cx.bsched, cx.gxe_std
-    S, emit_g_park = cx.S, cx.emit_g_park
-    cat, U, ncb, d1, NOXN = cx.block_info(ci)
-    if STL:
-        A('    stamp(9);   // (light stamps: all sub-steps of the block)')
-    if HOIST:   # the next block's first sub-step: its slab request goes out BEFORE this block's stores
-        A('    if (sidx + 1 < NSUB' + (' && !(diag & 32)' if exp else '') + ') stage_load(sidx + 1, (buf ^ 1));')
-        A('    __builtin_amdgcn_sched_barrier(0);')
+def _rev_stores(cx: _Gen, ci: int):
+    """g_xe stores of block ci: every edge its own row"""
+    A, exp, gxe_std = cx.A, cx.exp, cx.gxe_std
+    cat, U, ncb, d1, _ = cx.block_info(ci)
     A('    if (GX && g_xe && valid' + (' && !(diag & 16)' if exp else '') + ') {')
     A('      if constexpr (F16) {   // the bodies ran on raw matrix accumulators and scaled g_out entries: back to g_x itself')
     A('#pragma unroll')
@@ -978,6 +1063,20 @@ def _rev_block_end(cx: _Gen, ci: int):
             # 8.9 GB written for 5.9 GB of output in round 2)
             A(f'      __builtin_nontemporal_store(gx[{u}][{m}], reinterpret_cast<f32x4 *>(o + {m * cat.mul if gxe_std else 16 * m}));')
     A('    }')
+
+
+def _rev_block_end(cx: _Gen, ci: int):
+    """g_xe stores of the block (behind the hoisted slab request), the next block's g_out entries parked, rows rotated"""
+    A, exp, STL, HOIST, bsched, gxe_std = cx.A, cx.exp, cx.STL, cx.HOIST, cx.bsched, cx.gxe_std
+    S, emit_g_park = cx.S, cx.emit_g_park
+    cat, U, ncb, d1, NOXN = cx.block_info(ci)
+    if STL:
+        A('    stamp(9);   // (light stamps: all sub-steps of the block)')
+    if HOIST:   # the next block's first sub-step: its slab request goes out BEFORE this block's stores
+        A('    if (sidx + 1 < NSUB' + (' && !(diag & 32)' if exp else '') + ') stage_load(sidx + 1, (buf ^ 1));')
+        A('    __builtin_amdgcn_sched_barrier(0);')
+    if not cx.MG:
+        _rev_stores(cx, ci)
     # park the prefetched entries of the next block in the other buffer (last read one block ago)
     if ncb > 1:
         A(f'    if (cb + 1 < {ncb}) {{')
@@ -990,6 +1089,8 @@ def _rev_block_end(cx: _Gen, ci: int):
         emit_g_park('    ', ci + 1, 'gbuf ^ 1')
     A('    gbuf ^= 1;')
     A('    __builtin_amdgcn_wave_barrier();')
+    if cx.MG:   # (behind the park: the chain walks then run without the prefetched g_out entries in registers -- in front of it the
+        _rev_merge_stores(cx, ci)   #  SevenNet-0 middle layer spilled 12)
     if ncb > 1 and NOXN:
         A(f'    if (cb + 1 < {ncb}) {{')
         for u in range(U):
@@ -1243,7 +1344,7 @@ def _emit_reverse_kernel(cx: _Gen):
     for ci, bs in enumerate(cx.bsched):
         _rev_block_top(cx, ci)
         for si_, (ta, tb) in enumerate(bs['steps']):
-            _rev_substep(cx, ci, si_, ta, tb)
+            _rev_substep(cx, ci, si_, ta, tb, last=si_ + 1 == len(bs['steps']))
         _rev_block_end(cx, ci)
     _rev_tail(cx)
     _rev_epilogue(cx)
@@ -1608,6 +1709,37 @@ def _emit_launch_bwd(cx: _Gen):
     A('}')
 
 
+def _emit_launch_bwd_merged(cx: _Gen):
+    """launcher of the merged-store instantiation: the tangent-mode kernel's configuration per precision mode (so a window of the merge
+    map is the NWV tiles one workgroup takes), always with the source-row gradient"""
+    A, bwd_cfg, tag = cx.A, cx.bwd_cfg, cx.tag
+    A('template <int NT, bool F16, int NWV, bool GLDS, int OCC>')
+    A('void launch_bwd_t(const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,')
+    A('                  const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles,')
+    A('                  const void *slabs, float scale, const float *g_out, float *g_xe, const int32_t *merge_row, const int32_t *merge_next,')
+    A('                  float *g_vec, snet::FusedTail tail, hipStream_t st) {')
+    A('  const unsigned grid = (unsigned)((n_tiles + NWV - 1) / NWV);')
+    A(f'  conv_bwdftm_{tag}<NT, F16, NWV, GLDS, OCC, true><<<dim3(grid), dim3(64 * NWV), 0, st>>>(x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node,')
+    A('      (int)n_tiles, static_cast<const u32x4 *>(slabs), scale, g_out, g_xe, nullptr, g_vec, tail, 0, merge_row, merge_next);')
+    A('}')
+    A('void launch_bwd_merged(int nt, const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,')
+    A('                       const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles,')
+    A('                       const void *slabs, float scale, const float *g_out, float *g_xe, const int32_t *merge_row, const int32_t *merge_next,')
+    A('                       float *g_vec, snet::FusedTail tail, hipStream_t st) {')
+    args_b = 'x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, slabs, scale, g_out, g_xe, merge_row, merge_next, g_vec, tail, st'
+    w, gl, oc = bwd_cfg(2)
+    A(f'  if (nt == 4) launch_bwd_t<2, true, {w}, {"true" if gl else "false"}, {oc}>({args_b});')
+    for nt_, kw in ((3, 'else if'), (2, 'else if'), (1, 'else')):
+        w, gl, oc = bwd_cfg(nt_)
+        cond = f' (nt == {nt_})' if kw != 'else' else ''
+        A(f'  {kw}{cond} launch_bwd_t<{nt_}, false, {w}, {"true" if gl else "false"}, {oc}>({args_b});')
+    A('}')
+    windows = [0] + [bwd_cfg(n)[0] for n in (1, 2, 3)] + [bwd_cfg(2)[0]]
+    A(f'const snet::FusedMergedKernels kernels = {{"{tag}", {{{", ".join(str(v) for v in windows)}}}, launch_bwd_merged}};')
+    A('const snet::FusedMergedRegistrar registrar(&kernels);')
+    A('}  // namespace')
+
+
 def _emit_launch_fwd(cx: _Gen):
     A, tag, exp, def_f, fwd_cfg = cx.A, cx.tag, cx.exp, cx.def_f, cx.fwd_cfg
     A('template <int NT, bool F16, int NWV, bool GLDS, int OCC>')
@@ -1681,6 +1813,29 @@ def gen_conv_fused_tangent(spec: ConvSpec) -> str:
     _emit_reverse_kernel(cx)
     _emit_launch_bwd(cx)
     _emit_registration(cx)
+    return '\n'.join(cx.L) + '\n'
+
+
+def merged_store_class(spec: ConvSpec) -> bool:
+    """the shapes that get the merged-store instantiation: the packed-tile class running in tangent mode (two waves per SIMD with
+    register headroom, LDS freed by tangent mode -- the SevenNet-0 middle layers; the lmax-3 middle layers keep the reverse-mode
+    kernel at 256 registers)"""
+    if not fusable(spec) or spec.irreps_out.dim < spec.irreps_x.dim:   # (scalar-output last layers: the hosts take g_h from the
+        return False                                                      #  transposed convolution, no g_xe is written)
+    cx = _Gen(spec, tangent=True)
+    return cx.XT and cx.TGPREF and not cx.gxe_std
+
+
+def gen_conv_fused_tangent_merged(spec: ConvSpec) -> str:
+    """the merged-store instantiation of the tangent-mode reverse kernel (translation unit convftm_<tag>.hip, a registry entry of its
+    own): g_xe rows with the same source inside a workgroup's window of tiles are added in LDS before the store"""
+    cx = _Gen(spec, tangent=True, merged=True)
+    assert not cx.gxe_std
+    cx.exp = False   # (the kernel-tuning variants and their diag switches stay with the two other translation units)
+    _emit_header(cx)
+    _emit_path_functions(cx)
+    _emit_reverse_kernel(cx)
+    _emit_launch_bwd_merged(cx)
     return '\n'.join(cx.L) + '\n'
 
 

@@ -39,6 +39,16 @@ const FusedTangentKernels *find_fused_tangent(const char *tag) {
     if (std::string(k->tag) == tag) return k;
   return nullptr;
 }
+static std::vector<const FusedMergedKernels *> &fused_merged_registry() {
+  static std::vector<const FusedMergedKernels *> r;
+  return r;
+}
+void register_fused_merged(const FusedMergedKernels *k) { fused_merged_registry().push_back(k); }
+const FusedMergedKernels *find_fused_merged(const char *tag) {
+  for (const FusedMergedKernels *k : fused_merged_registry())
+    if (std::string(k->tag) == tag) return k;
+  return nullptr;
+}
 
 // Small scratch for deterministic two-stage reductions, per host thread and device (grown on
 // demand, never shrunk).  Per-thread because the partial-sum kernel and its final-sum kernel are
@@ -69,6 +79,7 @@ struct snet_conv_plan {
 struct snet_fused_plan {
   const snet::FusedKernels *k;
   const snet::FusedTangentKernels *kt;  // the shape's tangent-mode reverse kernel (nullptr: not compiled in)
+  const snet::FusedMergedKernels *km;   // its merged-store instantiation (nullptr: the shape has none)
   int terms;
   void *slabs;    // device: W2 as pre-split MFMA fragments in the FORWARD kernel's sub-step order
   void *slabs_b;  // the same in the REVERSE kernel's order, then the hidden-layer tail
@@ -177,7 +188,7 @@ int snet_fused_plan_create(const snet_conv_plan *plan, const snet_mlp_plan *mlp,
     snet::set_error("snet_fused_plan_create: device allocation / upload of the W2 fragment stream failed");
     return 1;
   }
-  *out = new snet_fused_plan{k, snet::find_fused_tangent(plan->k->tag), terms, dev, dev_b, hid, {exps[0], exps[1], exps[2]}};
+  *out = new snet_fused_plan{k, snet::find_fused_tangent(plan->k->tag), snet::find_fused_merged(plan->k->tag), terms, dev, dev_b, hid, {exps[0], exps[1], exps[2]}};
   return 0;
 }
 int snet_fused_plan_tile_mode(const snet_fused_plan *p) { return p ? p->k->tile_mode : 0; }
@@ -263,6 +274,36 @@ int snet_conv_bwd_fused_tangent(const snet_fused_plan *fp, const float *x, const
   fp->kt->bwd(fp->terms, x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, fp->slabs_b, scale, g_out, g_xe, nullptr,
               g_vec, tail, static_cast<hipStream_t>(stream));
   SNET_CHECK_LAUNCH("snet_conv_bwd_fused_tangent");
+  return 0;
+}
+int snet_fused_plan_merge_window(const snet_fused_plan *fp) {
+  // (terms = 3, three bf16 terms: the merged-store instantiation of the SevenNet-0 middle layer spills 36 registers there, the
+  // tangent-mode kernel 4, and it has not been measured -- that mode keeps one row per edge)
+  return (fp != nullptr && fp->km != nullptr && fp->kt != nullptr && fp->kt->tangent_pref != 0 && fp->terms != 3) ? fp->km->window[fp->terms] : 0;
+}
+int snet_conv_bwd_fused_tangent_merged(const snet_fused_plan *fp, const float *x, const float *sh, const float *dsh, const float *h2,
+                                       const float *h2d, const int32_t *w_row, const int32_t *row_ptr, const int32_t *src,
+                                       const int32_t *tile_ptr, const int32_t *tile_node, int64_t n_tiles, float scale,
+                                       const float *g_out, float *g_xe, const int32_t *merge_row, const int32_t *merge_next,
+                                       const float *edge_vec, float *g_vec, const float *x_rowmax, const float *g_rowmax, void *stream) {
+  const char *who = "snet_conv_bwd_fused_tangent_merged";
+  SNET_REQUIRE(fp != nullptr, std::string(who) + ": null plan");
+  SNET_REQUIRE(fp->km != nullptr, std::string(who) + ": this shape has no merged-store kernel (snet_fused_plan_merge_window() == 0)");
+  SNET_REQUIRE(fp->terms != 4 || (x_rowmax != nullptr && g_rowmax != nullptr),
+               std::string(who) + ": terms = 4 (fp16 operands) needs x_rowmax and g_rowmax (snet_row_absmax of x and g_out)");
+  SNET_REQUIRE(n_tiles < (1ll << 31), std::string(who) + ": too many tiles");
+  if (n_tiles <= 0) return 0;
+  SNET_REQUIRE(tile_ptr != nullptr && tile_node != nullptr, std::string(who) + ": null tile list");
+  SNET_REQUIRE(g_xe != nullptr && merge_row != nullptr && merge_next != nullptr, std::string(who) + ": g_xe and the merge map are required");
+  SNET_REQUIRE(h2d != nullptr && edge_vec != nullptr && dsh != nullptr && g_vec != nullptr,
+               std::string(who) + ": h2d, edge_vec, dsh and g_vec are required");
+  snet::FusedTail tail{nullptr, nullptr, fp->hidden.nb, fp->hidden.act, fp->hidden.cst, fp->exps[0], fp->exps[1], fp->exps[2],
+                       x_rowmax, g_rowmax, nullptr};
+  tail.h2d = h2d;
+  tail.edge_vec = edge_vec;
+  fp->km->bwd(fp->terms, x, sh, dsh, h2, w_row, row_ptr, src, tile_ptr, tile_node, n_tiles, fp->slabs_b, scale, g_out, g_xe, merge_row,
+              merge_next, g_vec, tail, static_cast<hipStream_t>(stream));
+  SNET_CHECK_LAUNCH(who);
   return 0;
 }
 int snet_conv_bwd_fused_sh(const snet_fused_plan *fp, const float *x, const float *sh, const float *h2, const int32_t *w_row,

@@ -127,6 +127,22 @@ const FusedTangentKernels *find_fused_tangent(const char *tag);
 struct FusedTangentRegistrar {
   explicit FusedTangentRegistrar(const FusedTangentKernels *k) { register_fused_tangent(k); }
 };
+// the merged-store instantiation of the tangent-mode reverse kernel (generated convftm_<tag>.hip; the packed-tile class only): g_xe is a
+// COMPACT buffer of merged rows, merge_row / merge_next the per-edge merge map of snet_gxe_merge_map built with window[terms] tiles per
+// window (the tiles one workgroup takes in that precision mode).  g_vec as FusedTangentKernels::bwd writes it, bit for bit.
+struct FusedMergedKernels {
+  const char *tag;
+  int window[5];  // by precision mode (terms 1 .. 4; [0] unused)
+  void (*bwd)(int nt, const float *x, const float *sh, const float *dsh, const float *h2, const int32_t *w_row,
+              const int32_t *row_ptr, const int32_t *src, const int32_t *tile_ptr, const int32_t *tile_node,
+              int64_t n_tiles, const void *slabs, float scale, const float *g_out, float *g_xe, const int32_t *merge_row,
+              const int32_t *merge_next, float *g_vec, FusedTail tail, hipStream_t st);
+};
+void register_fused_merged(const FusedMergedKernels *k);
+const FusedMergedKernels *find_fused_merged(const char *tag);
+struct FusedMergedRegistrar {
+  explicit FusedMergedRegistrar(const FusedMergedKernels *k) { register_fused_merged(k); }
+};
 // host copy of the radial MLP's pre-normalised last-layer weights W2'[64, wn] (row-major)
 const float *mlp_plan_w2_host(const snet_mlp_plan *plan);
 // W2'[64, wn] -> device stream of 1-KB fragment lines, per sub-step: [tile(2)][kstep(2)][term(nt)] (the

@@ -392,6 +392,18 @@ struct snet_model {
     const char *e = getenv("SNET_LAST_LAYER_MERGED");
     return e == nullptr || strcmp(e, "0") != 0;
   }();
+  // Merged g_xe stores of the middle layers (snet_conv_bwd_fused_tangent_merged over snet_gxe_merge_map, engine.py's `merge_gxe`): on
+  // where the topology cache keeps the map with the tile list (its host pass is paid per graph, not per evaluation) and the graph
+  // merges enough (SNET_GXE_MERGE_MAX_RATIO, engine.py's GXE_MERGE_MAX_RATIO); snet_model_set_gxe_merge(0) or SNET_GXE_MERGE=0 keep
+  // one g_xe row per edge.
+  bool gm_mode = [] {
+    const char *e = getenv("SNET_GXE_MERGE");
+    return e == nullptr || strcmp(e, "0") != 0;
+  }();
+  int32_t *c_merge_row = nullptr, *c_merge_next = nullptr, *c_merge_seg = nullptr, *c_merge_perm = nullptr;
+  size_t c_merge_ecap = 0, c_merge_ncap = 0;
+  int64_t c_merge_rows = 0;
+  int c_merge_window = 0;             // window the cached map was built with (0: none cached)
   bool l0_shape_ok = false;           // layer 0's shape and radial network are inside snet_layer0_plan_create's domain
   std::vector<float> h0_host;         // host copy of h0_table
   struct L0Plan { snet_layer0_plan *plan; int32_t *slot; int n_slots; };
@@ -402,6 +414,7 @@ struct snet_model {
 };
 
 constexpr int64_t OVERLAP_MAX_EDGES = 1000000;  // same policy as engine.py
+constexpr double SNET_GXE_MERGE_MAX_RATIO = 0.8;  // engine.py's GXE_MERGE_MAX_RATIO
 
 namespace {
 
@@ -715,6 +728,7 @@ extern "C" void snet_model_destroy(snet_model *m) {
   for (hipEvent_t e : {m->ev_h0, m->ev_h1}) if (e) (void)hipEventDestroy(e);
   for (void *d : {(void *)m->embed, (void *)m->scale, (void *)m->shift, (void *)m->h0_table, (void *)m->sc0_table, (void *)m->ro_v, (void *)m->c_tile_ptr, (void *)m->c_tile_node,
                   (void *)m->c_center_t, (void *)m->c_w_row_t, (void *)m->c_tile_ptr_b, (void *)m->c_ptile_e0, (void *)m->c_ptile_nodes, (void *)m->arena.base,
+                  (void *)m->c_merge_row, (void *)m->c_merge_next, (void *)m->c_merge_seg, (void *)m->c_merge_perm,
                   (void *)m->species_rows})
     if (d) (void)hipFree(d);
   delete m;
@@ -779,6 +793,12 @@ extern "C" int snet_model_set_layer0_moments(snet_model *m, int32_t enable) {
 extern "C" int snet_model_set_last_layer_merged(snet_model *m, int32_t enable) {
   SNET_REQUIRE(m != nullptr, "snet_model_set_last_layer_merged: null model");
   m->ll_mode = enable != 0;
+  return 0;
+}
+
+extern "C" int snet_model_set_gxe_merge(snet_model *m, int32_t enable) {
+  SNET_REQUIRE(m != nullptr, "snet_model_set_gxe_merge: null model");
+  m->gm_mode = enable != 0;
   return 0;
 }
 
@@ -895,6 +915,7 @@ struct Eval {
   int64_t tile_k = 0;
   int32_t *ptile_e0 = nullptr, *ptile_nodes = nullptr;   // packed tiles: the interior rows' [0, ptile_k) in front of the boundary rows'
   int64_t pn_tiles = 0, ptile_k = 0;
+  int merge_window = 0;   // > 0: the layers whose merged-store kernel takes this window run it, over the model's cached merge map
   int32_t *center_t = nullptr, *w_row_t = nullptr;  // edges grouped by source (transposed scalar convolution)
   float *sh_t = nullptr;
   float *gw_buf[2] = {nullptr, nullptr};   // g_w double buffer (its reader runs on the side stream)
@@ -994,6 +1015,41 @@ int topo_lists(snet_model *m, bool grow, int32_t *&c0, size_t bytes0, int32_t *&
   return 0;
 }
 
+// merge map of the merged-store reverse kernels over the packed tile list, cut where the list is cut: kept with the topology cache
+int merge_map(snet_model *m, Eval &e) {
+  e.merge_window = 0;
+  if (!m->gm_mode || !m->topo_cache || !e.need_tiles[1] || e.E <= 0) return 0;
+  int window = 0;   // one map per graph: the window of the first layer that has a merged-store kernel (the middle layers share a shape)
+  for (int t = 1; t < e.Lc && window == 0; ++t)
+    if (m->layers[t].fused && m->layers[t].tfused == nullptr && m->layers[t].tile_mode == 1)   // (the map is built over the packed list)
+      window = snet_fused_plan_merge_window(m->layers[t].fused);
+  if (window == 0) return 0;
+  if (!(e.topo_hit && m->c_merge_window == window)) {
+    m->c_merge_window = 0;
+    if (m->c_merge_ecap < (size_t)e.E || m->c_merge_ncap < (size_t)e.NT + 1) {
+      for (int32_t **p : {&m->c_merge_row, &m->c_merge_next, &m->c_merge_seg, &m->c_merge_perm}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+      m->c_merge_ecap = (size_t)e.E + (size_t)e.E / 8 + 64;
+      m->c_merge_ncap = (size_t)e.NT + (size_t)e.NT / 8 + 64;
+      const bool ok = hipMalloc((void **)&m->c_merge_row, m->c_merge_ecap * 4) == hipSuccess &&
+                      hipMalloc((void **)&m->c_merge_next, m->c_merge_ecap * 4) == hipSuccess &&
+                      hipMalloc((void **)&m->c_merge_perm, m->c_merge_ecap * 4) == hipSuccess &&
+                      hipMalloc((void **)&m->c_merge_seg, m->c_merge_ncap * 4) == hipSuccess;
+      if (!ok) m->c_merge_ecap = m->c_merge_ncap = 0;
+      SNET_REQUIRE(ok, "snet_model_eval: alloc");
+    }
+    if (int rc = snet_gxe_merge_map(e.row_ptr, e.src, e.ptile_e0, e.ptile_nodes, e.pn_tiles, e.ptile_k, 1, window, e.N, e.NT, e.E, m->c_merge_row,
+                                    m->c_merge_next, m->c_merge_seg, m->c_merge_perm, &m->c_merge_rows, e.st))
+      return rc;
+    m->eval_syncs += 2;   // (the builder reads the index arrays back and waits for its upload)
+    m->c_merge_window = window;
+  }
+  if ((double)m->c_merge_rows <= SNET_GXE_MERGE_MAX_RATIO * (double)e.E) e.merge_window = window;
+  return 0;
+}
+
 // ---- topology-only work: rebuilt unless the cache holds it for exactly these index arrays
 int topology(snet_model *m, Eval &e) {
   const int64_t NT = e.NT, N = e.N, E = e.E, n_int = e.n_int;
@@ -1048,6 +1104,7 @@ int topology(snet_model *m, Eval &e) {
       m->c_ptile_k = e.ptile_k;
     }
   }
+  if ((rc = merge_map(m, e))) return rc;
   if (e.any_transposed && E > 0) {  // edges grouped by source (transposed scalar convolution)
     const bool grow = m->topo_cache && m->c_edge_cap < (size_t)E + 64;
     if (grow) m->c_edge_cap = (size_t)E + 64;
@@ -1415,8 +1472,13 @@ int reverse_layer_fused(snet_model *m, Eval &e, int t, const float *g_y, const f
   const bool tail = tg || snet_fused_plan_has_mlp_tail(L.fused) != 0;   // nothing of the radial branch left to reverse afterwards
   float *g_h2 = tail ? nullptr : A.f((size_t)E * 64);
   float *x_max = e.x_max_of[t];   // (bounds of every edge's g_w, see snet_row_absmax; computed before the layer loop)
+  // merged g_xe rows (snet_gxe_merge_map): g_xe is the compact buffer, summed over the map's own segment lists
+  const bool mg = tg && t > 0 && !transposed && L.tile_mode == 1 && e.merge_window > 0 && snet_fused_plan_merge_window(L.fused) == e.merge_window;
   auto bwd_tiles = [&](const int32_t *tp, const int32_t *tn, int64_t nt) -> int {
     if (E <= 0 || nt <= 0 || merged) return 0;   // (merged: gh_rows adds to g_vec too)
+    if (mg)
+      return snet_conv_bwd_fused_tangent_merged(L.fused, s.h, sh, dsh, s.w, s.wd, w_row, row_ptr, src, tp, tn, nt, L.conv_scale, g_m, g_xe,
+                                                m->c_merge_row, m->c_merge_next, edge_vec, g_vec, x_max, g_max, st);
     if (tg)
       return snet_conv_bwd_fused_tangent(L.fused, s.h, sh, dsh, s.w, s.wd, w_row, row_ptr, src,
                                          tp, tn, nt, L.conv_scale, g_m, g_xe, edge_vec, g_vec, x_max, g_max, st);
@@ -1429,6 +1491,10 @@ int reverse_layer_fused(snet_model *m, Eval &e, int t, const float *g_y, const f
     if (t == 0 && e.l0 != nullptr)   // transposed grouped GEMM per atom, then one pass over the edges: g_vec += spherical and radial part
       return snet_layer0_conv_bwd(e.l0->plan, g_m, s.w, s.wd, w_row, row_ptr, src, types, e.l0->slot, sh,
                                   dsh, edge_vec, N, A.f(e.l0_scratch), g_vec, st);
+    if (mg && e.ptile_k > 0) {   // the map's windows follow the list's cut: a cut list is launched as its two sub-lists
+      if (int rc1 = bwd_tiles(e.ptile_e0, e.ptile_nodes, e.ptile_k)) return rc1;
+      return bwd_tiles(e.ptile_e0 + e.ptile_k, e.ptile_nodes + 2 * e.ptile_k, e.pn_tiles - e.ptile_k);
+    }
     return packed ? bwd_tiles(e.ptile_e0, e.ptile_nodes, e.pn_tiles) : bwd_tiles(e.tile_ptr, e.tile_node, e.n_tiles);
   };
   if (!rsplit && (rc = bwd_all())) return rc;
@@ -1444,7 +1510,8 @@ int reverse_layer_fused(snet_model *m, Eval &e, int t, const float *g_y, const f
       if (transposed)
         return snet_conv_fwd_fused(L.tfused, g_m, e.sh_t, s.w, e.w_row_t, col_ptr + a, e.center_t, b - a, L.conv_scale,
                                    g_h + (size_t)a * L.dx, st);
-      return snet_segment_sum_rows_chunked(g_xe, col_ptr + a, eperm, b - a, L.dx, L.gxe_chunks, g_h + (size_t)a * L.dx, st);
+      return snet_segment_sum_rows_chunked(g_xe, (mg ? m->c_merge_seg : col_ptr) + a, mg ? m->c_merge_perm : eperm, b - a, L.dx, L.gxe_chunks,
+                                           g_h + (size_t)a * L.dx, st);
     };
     if (transposed && !merged)
       for (size_t i = 0; i + 1 < L.t_dead.size(); i += 2)

@@ -72,6 +72,7 @@ class Graph:
     n_interior: int = 0
     _tile_split: Optional[tuple] = None
     _tiles_packed: Optional[tuple] = None
+    _merge_maps: Optional[dict] = None
     # batch of B systems (sevennet_amd.batch): atoms of system b are the rows [seg_ptr[b], seg_ptr[b+1]); edges never cross
     # systems.  Device int32 [B+1] and its host copy; None = one system
     seg_ptr: Optional[torch.Tensor] = None
@@ -125,6 +126,27 @@ class Graph:
                                                _stream()), 'snet_edge_tiles')
             self.tile_ptr, self.tile_node, self.n_tiles = tp, tn, int(n.value)
         return self.tile_ptr, self.tile_node, self.n_tiles
+
+    def merge_map(self, mode: int, window: int):
+        """merge map of the merged-store reverse kernels (snet_gxe_merge_map) over this graph's tile list of `mode`, `window` tiles per
+        workgroup, cut where the list is cut -> (merge_row[E], merge_next[E], seg_ptr[n_total + 1], perm[n_rows], n_rows), built on
+        first use"""
+        if self._merge_maps is None:
+            self._merge_maps = {}
+        if (mode, window) not in self._merge_maps:
+            assert mode == 1, 'the hosts merge over packed tiles only'
+            lib = _lib.load()
+            dev = self.edge_vec.device
+            tp, tn, nt = self.tiles(1)
+            with torch.cuda.device(dev):
+                mr, mn, pm = (torch.empty(self.n_edges, dtype=torch.int32, device=dev) for _ in range(3))
+                sp = torch.empty(self.n_total + 1, dtype=torch.int32, device=dev)
+                n = C.c_int64()
+                _lib.check(lib.snet_gxe_merge_map(_ptr(self.row_ptr), _ptr(self.src), _ptr(tp), _ptr(tn), nt, self._tiles_packed[3], 1, window,
+                                                  self.n_local, self.n_total, self.n_edges, _ptr(mr), _ptr(mn), _ptr(sp), _ptr(pm),
+                                                  C.byref(n), _stream()), 'snet_gxe_merge_map')
+            self._merge_maps[(mode, window)] = (mr, mn, sp, pm[:n.value], int(n.value))
+        return self._merge_maps[(mode, window)]
 
     def tiles_split(self, mode: int = 0):
         """the tile list cut at n_interior: ((tile_ptr, tile_node, n) of the interior rows, (tile_ptr', tile_node', n') of the
@@ -323,12 +345,15 @@ class _Span:
 
 class HipForceEngine:
     OVERLAP_MAX_EDGES = 1_000_000
+    # merged rows / edges of a graph at or below which the middle layers take the merged-store reverse kernel (the native
+    # host's SNET_GXE_MERGE_MAX_RATIO in csrc/snet_model.cpp is the same number)
+    GXE_MERGE_MAX_RATIO = 0.8
 
     def __init__(self, config: dict, state_dict: Dict[str, np.ndarray], device='cuda:0', mlp_mode: str = 'bf16x6',
                  linear_mode: str = 'bf16x6', fused='auto', fused_terms='f16x3', modal=None, overlap: bool = True,
                  mlp_tail: bool = True, transposed_conv: bool = True, species_tables: bool = True,
                  fold_readout: bool = True, tangent: bool = True, layer0_moments: bool = True,
-                 last_layer_merged: bool = True):
+                 last_layer_merged: bool = True, merge_gxe: bool = True):
         """mlp_mode / linear_mode: 'bf16x6' (split-precision MFMA, fp32-class accuracy, default) or
         'fp32' (exact fp32 MFMA) for the fused radial MLP / the node-level equivariant linears.
         fused: 'auto' (default) / True / False / 'fwd' / 'bwd' -- run the radial MLP's last layer INSIDE the
@@ -366,10 +391,10 @@ class HipForceEngine:
         last_layer_merged: the last layer's reverse pass (g_h and g_vec) in one source-grouped launch (snet_lastlayer_conv_bwd; DESIGN
         4l) where model_spec.lastlayer_merged_eligible allows it; False keeps the tangent-mode reverse kernel + the transposed
         convolution (A/B runs, the tests' reference).  The forward pass is the same either way.
+        merge_gxe: g_xe rows with the same source merged inside the reverse kernel's workgroups; see _init_gxe_merge.
         """
         self.fused_terms, self.fused_mode = self._check_modes(mlp_mode, linear_mode, fused, fused_terms)
-        self.mlp_mode = mlp_mode
-        self.linear_mode = linear_mode
+        self.mlp_mode, self.linear_mode = mlp_mode, linear_mode
         self.overlap, self.halo_split = bool(overlap), True   # False: exchange, then the whole convolution (A/B measurements of the overlap)
         self._side = None  # second stream, created on first use
         self._acc_descs = {}  # id(descriptor array) -> its all-accumulating copy (the arrays live as long as the engine)
@@ -520,10 +545,28 @@ class HipForceEngine:
             self.scale = torch.tensor(sc_v, dtype=torch.float32, device=self.dev)
             self.shift = torch.tensor(sh_v, dtype=torch.float32, device=self.dev)
             self.scale0 = float(sc_v[0])
-        self.act_radial = ACT_ID[sp.act_radial]
-        self.act_cst = ACT_CST[sp.act_radial]
+        self.act_radial, self.act_cst = ACT_ID[sp.act_radial], ACT_CST[sp.act_radial]
         self.needs_species_rows = any(ls.sc is not None and ls.sc.n_species for ls in sp.layers)
         self._init_layer0(layer0_moments)
+        self._init_gxe_merge(merge_gxe)
+
+    def _init_gxe_merge(self, on: bool):
+        """merge_gxe: the middle layers' reverse kernel adds the g_xe rows that share their source inside a workgroup's window of tiles
+        in LDS and writes them once, into a compact buffer that the segment sum then reads (snet_conv_bwd_fused_tangent_merged over
+        Graph.merge_map).  Per layer: L.merge_window = tiles per window, 0 where the shape has no such kernel (only the
+        packed-tile class in tangent mode does) or the layer writes no g_xe (first layer, transposed / one-launch last layer).  Per
+        graph: taken where merged rows / edges <= GXE_MERGE_MAX_RATIO -- an atom order without locality merges nothing and keeps
+        today's kernel.  False: today's path everywhere (A/B runs, the tests' reference)."""
+        for t, L in enumerate(self.layers):
+            uses_gxe = t > 0 and L.fused_bwd and L.tangent and getattr(L, 'tplan', None) is None
+            L.merge_window = int(self.lib.snet_fused_plan_merge_window(L.fplan)) if (on and uses_gxe and L.tile_mode == 1) else 0
+
+    def _gxe_merge(self, L, g):
+        """the graph's merge map for layer L, or None where the layer / the graph keeps one g_xe row per edge"""
+        if not L.merge_window or g.n_edges == 0:
+            return None
+        mm = g.merge_map(L.tile_mode, L.merge_window)
+        return mm if mm[4] <= self.GXE_MERGE_MAX_RATIO * g.n_edges else None
 
     @staticmethod
     def _check_modes(mlp_mode, linear_mode, fused, fused_terms):
@@ -1074,7 +1117,8 @@ class HipForceEngine:
             # layer 0: inputs depend on species only -> no source-row gradient needed
             use_t = t > 0 and getattr(L, 'tplan', None) is not None and E > 0
             use_m = use_t and L.mplan is not None   # g_h and g_vec of the layer from one launch per range of source rows
-            g_xe = self._new(E, ls.si1.dim_out) if (t > 0 and not use_t) else None
+            mm = self._gxe_merge(L, g) if (t > 0 and not use_t) else None   # merged g_xe rows: a compact buffer and its own segment lists
+            g_xe = self._new(mm[4] if mm else E, ls.si1.dim_out) if (t > 0 and not use_t) else None
             g_w = g_h2 = None
             # reverse split (t > 0, fused kernels): boundary tiles first -- they hold every edge with a ghost source --
             # then the ghost rows of g_h, whose exchange starts at once; interior tiles, the local rows and sc^T run under it
@@ -1094,7 +1138,7 @@ class HipForceEngine:
                 sum of the per-edge rows the reverse kernel wrote"""
                 if b <= a:
                     return
-                cp, go = C.c_void_p(g.col_ptr.data_ptr() + 4 * a), C.c_void_p(g_h.data_ptr() + 4 * a * ls.si1.dim_out)
+                cp, go = C.c_void_p((mm[2] if mm else g.col_ptr).data_ptr() + 4 * a), C.c_void_p(g_h.data_ptr() + 4 * a * ls.si1.dim_out)
                 if use_m:
                     with _Span(self, f'conv_bwd_merged[{ls.conv.tag}]'):
                         _lib.check(lib.snet_lastlayer_conv_bwd(L.mplan, _ptr(h), _ptr(g_m), _ptr(sh), _ptr(dsh), _ptr(g.edge_vec), _ptr(h2),
@@ -1108,7 +1152,7 @@ class HipForceEngine:
                     return
                 with _Span(self, 'conv_bwd_node[segment_sum]'):
                     if L.fused_bwd:   # the fused kernel's g_xe rows: chunk order undone while summing
-                        _lib.check(lib.snet_segment_sum_rows_chunked(_ptr(g_xe), cp, _ptr(g.eperm), b - a, ls.si1.dim_out,
+                        _lib.check(lib.snet_segment_sum_rows_chunked(_ptr(g_xe), cp, _ptr(mm[3] if mm else g.eperm), b - a, ls.si1.dim_out,
                                                                      _ptr(L.gxe_chunks), go, st), 'snet_segment_sum_rows_chunked')
                     else:
                         _lib.check(lib.snet_segment_sum_rows(_ptr(g_xe), cp, _ptr(g.eperm), b - a, ls.si1.dim_out, go, st),
@@ -1123,13 +1167,19 @@ class HipForceEngine:
                     if nt_ <= 0 or use_m:   # (merged: gh_rows writes g_vec too)
                         return
                     with _Span(self, f'conv_bwd_fused[{ls.conv.tag}]'):
-                        if tangent:
+                        if mm:
+                            _lib.check(lib.snet_conv_bwd_fused_tangent_merged(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(h2d), _ptr(w_row),
+                                                                              _ptr(g.row_ptr), _ptr(g.src), _ptr(tp_), _ptr(tn_), nt_, L.scale,
+                                                                              _ptr(g_m), _ptr(g_xe), _ptr(mm[0]), _ptr(mm[1]), _ptr(g.edge_vec),
+                                                                              _ptr(g_vec), _ptr(x_max), _ptr(g_max), st),
+                                       'snet_conv_bwd_fused_tangent_merged')
+                        elif tangent:
                             _lib.check(lib.snet_conv_bwd_fused_tangent(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(h2d), _ptr(w_row),
                                                                        _ptr(g.row_ptr), _ptr(g.src), _ptr(tp_), _ptr(tn_), nt_, L.scale,
                                                                        _ptr(g_m), _ptr(g_xe), _ptr(g.edge_vec), _ptr(g_vec), _ptr(x_max),
                                                                        _ptr(g_max), st), 'snet_conv_bwd_fused_tangent')
-                            return
-                        _lib.check(lib.snet_conv_bwd_fused(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(w_row),
+                        else:
+                            _lib.check(lib.snet_conv_bwd_fused(L.fplan, _ptr(h), _ptr(sh), _ptr(dsh), _ptr(h2), _ptr(w_row),
                                                            _ptr(g.row_ptr), _ptr(g.src), _ptr(tp_), _ptr(tn_), nt_, L.scale,
                                                            _ptr(g_m), _ptr(g_xe), _ptr(g_h2),
                                                            _ptr(emb) if L.mlp_tail else None, _ptr(g_emb) if L.mlp_tail else None,
@@ -1151,8 +1201,9 @@ class HipForceEngine:
                     gh_rows(0, N)
                 elif l0 is not None:
                     self._layer0_bwd(c, g_m, h2, h2d, g_vec)
-                elif E > 0:
-                    bwd_tiles(*g.tiles(L.tile_mode))
+                elif E > 0:   # (the merge map's windows follow the list's cut: a cut list is launched as its two sub-lists)
+                    for part in (g.tiles_split(1) if mm and g._tiles_packed[3] else (g.tiles(L.tile_mode),)):
+                        bwd_tiles(*part)
             else:
                 if side is not None:  # double-buffered: the MLP reverse of layer t+2 may still be reading this one
                     if gw_done[t & 1] is not None:

@@ -44,6 +44,8 @@ def shape_sources(spec: ConvSpec):
     if codegen_fused.fusable(spec):
         srcs.append((f'convf_{spec.tag}.hip', codegen_fused.gen_conv_fused(spec)))
         srcs.append((f'convft_{spec.tag}.hip', codegen_fused.gen_conv_fused_tangent(spec)))
+        if codegen_fused.merged_store_class(spec):
+            srcs.append((f'convftm_{spec.tag}.hip', codegen_fused.gen_conv_fused_tangent_merged(spec)))
     return srcs
 
 

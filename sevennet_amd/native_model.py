@@ -28,13 +28,13 @@ class _DevRows:
 
 class NativeModel:
     def __init__(self, model, state_dict: Optional[Dict[str, np.ndarray]] = None, device='cuda:0', modal=None, layer0_moments: Optional[bool] = None,
-                 last_layer_merged: Optional[bool] = None):
+                 last_layer_merged: Optional[bool] = None, merge_gxe: Optional[bool] = None):
         """model: path of a `.snet` file, or a reference config dict (then `state_dict` is required and
         the file is written to a temporary location first).
         layer0_moments: HipForceEngine's switch (snet_model_set_layer0_moments); None = the sequencer's default (on, unless
         SNET_LAYER0_MOMENTS=0 is in the environment).
         last_layer_merged: likewise for the last layer's one-launch reverse pass (snet_model_set_last_layer_merged,
-        SNET_LAST_LAYER_MERGED=0)."""
+        SNET_LAST_LAYER_MERGED=0), merge_gxe for the middle layers' merged g_xe stores (snet_model_set_gxe_merge, SNET_GXE_MERGE=0)."""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError('NativeModel needs a ROCm GPU (no CPU fallback exists)')
@@ -46,6 +46,8 @@ class NativeModel:
         if last_layer_merged is not None:
             _lib.check(self.lib.snet_model_set_last_layer_merged(self.handle, int(bool(last_layer_merged))),
                        'snet_model_set_last_layer_merged')
+        if merge_gxe is not None:
+            _lib.check(self.lib.snet_model_set_gxe_merge(self.handle, int(bool(merge_gxe))), 'snet_model_set_gxe_merge')
         cut, ns, nl = C.c_float(), C.c_int32(), C.c_int32()
         comm = (C.c_int32 * 64)()
         _lib.check(self.lib.snet_model_info(self.handle, C.byref(cut), C.byref(ns), C.byref(nl), comm, 64),

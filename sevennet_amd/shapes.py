@@ -59,6 +59,14 @@ def lastlayer_test_configs() -> Dict[str, dict]:
     }
 
 
+def merged_store_test_tags() -> List[str]:
+    """The 16-channel last-layer shapes of last16_l1 / last16_l2: built with the merged-store instantiation of the tangent-mode reverse
+    kernel as well (codegen_fused.gen_conv_fused_tangent_merged), for tests/test_gxe_merge_gpu.py only -- per-row tiles, one sub-step
+    per block, three x blocks: the generator's paths that the shipped class (codegen_fused.merged_store_class) does not take."""
+    cfgs = lastlayer_test_configs()
+    return [build_model_spec(cfgs[k]).layers[-1].conv.tag for k in ('last16_l1', 'last16_l2')]
+
+
 def aot_configs() -> Dict[str, dict]:
     return {
         'ts_example': TS_EXAMPLE_CONFIG,
